@@ -12,6 +12,11 @@ rows, up to 101 ADMM iterations of n agent QPs each) + 10 simulation steps (SO(3
     python bench.py --gpus N --batch 65536   (weak scaling: 65,536 scenarios per GPU)
     python bench.py --config C2|C3|C5 [--fixed-work]   (QP-level configs of SURVEY.md 8(d))
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+    python bench.py --full   (after the timed steps also the per-scenario metrics step, the 10 s sustained loop
+                              and the work-matched CPU baseline; a plain run sets up, warms up, times its --steps
+                              steps and prints the result line)
+    python bench.py --dump-outputs DIR   (the states the last timed step left, DIR/state.npy, DIR/hl_counter.npy;
+                                          the inputs are seeded: the same arguments give the same scenarios)
 
 The data path has no collective; RCCL over xGMI (sharding.Comm, libdat.so's dat_comm_* C-ABI: no PyTorch in
 the rank processes) carries the barrier, the max-over-ranks time and an all-gather of the per-scenario metrics.
@@ -127,7 +132,17 @@ def parse():
     ap.add_argument("--persistent-blocks", type=int, default=0,
                     help="resident k_cadmm / k_dd workgroups (0: the library default, 4 per CU); more workgroups "
                          "hold fewer scenario slots each (dat_set_persistent_blocks)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: the per-scenario metrics step after the timed steps "
+                         "(stats.mean_admm_iters, *_last_step), the sustained loop (--sustained-steps) and the CPU "
+                         "baseline (--no-cpu-baseline, --cpu-sample-s).  Off: set up, warm up, time --steps steps, "
+                         "print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left with the caller as DIR/<name>.npy "
+                         "(float64; at most 64 MB in all, a fixed seeded sample of the scenarios beyond that).  C4: "
+                         "state, hl_counter (get_state).  QP-level configs: f_des, iters, qp_status of the last step, "
+                         "whose copy-out is then inside the timed region.  With --gpus N > 1: <name>_rank<r>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample-s", type=float, default=15.0)
     ap.add_argument("--selftest", action="store_true",
                     help="CPU-only check of the launch / shard / combine path (gloo, no solver work, synthetic numbers)")
@@ -388,6 +403,30 @@ class _SelftestEngine:
                                qp_status=np.zeros((self.batch, self.n), dtype=np.int32))
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: write per-scenario output arrays (leading axis: scenario) as <out_dir>/<name>.npy in
+    float64 (<name>_rank<r>.npy when sharded over ranks), DUMP_BUDGET_BYTES at most in all.  Beyond that, a
+    fixed sample of the scenarios (seed 0, the same rows of every array, ascending; sample_index.npy holds
+    their scenario numbers), so that two builds run with the same arguments write comparable files."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    assert len(rows) == 1, rows
+    B = rows.pop()
+    row_bytes = sum(a.nbytes // max(B, 1) for a in arrays.values()) + 8  # (+ the sample index)
+    budget = DUMP_BUDGET_BYTES // world  # (every rank writes its own files)
+    if B * row_bytes > budget:
+        idx = np.sort(np.random.default_rng(0).choice(B, budget // row_bytes, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
+
+
 def timed_steps(eng, steps: int, barrier):
     """Run `steps` closed-loop HL periods back to back in one dat_closed_loop call, bracketed by the
     barrier + device synchronisation; returns (elapsed s, per-step ms array).  The per-step times are
@@ -519,15 +558,27 @@ def main():
     # per-class counters and the k_cadmm event time of the timed steps, read before the metrics step
     # below (its launch is not part of the timed region)
     class_w = [eng.class_work(k) for k in range(4)] if args.mode == "cadmm" else None
-    # per-scenario metrics of the last step (all-gathered over ranks: the only collective)
-    res = eng.control(None, None)
-    # per scenario: outer iterations, min env distance, collision flag, agent QPs not OPTIMAL
-    local_metrics = np.stack([res.iters.astype(np.float64), res.min_env_dist, res.collision.astype(np.float64),
-                              (np.asarray(res.qp_status) != 0).sum(axis=1).astype(np.float64)], 1)
+    if args.dump_outputs and not args.selftest:
+        # what closed_loop leaves with its caller: every scenario's state after the last timed step
+        st_out, hl_counter = eng.get_state()
+        dump_outputs(args.dump_outputs, {"state": st_out, "hl_counter": hl_counter}, rank, world)
+    if args.full:
+        # per-scenario metrics of the last step (all-gathered over ranks: the only collective)
+        res = eng.control(None, None)
+        # per scenario: outer iterations, min env distance, collision flag, agent QPs not OPTIMAL
+        local_metrics = np.stack([res.iters.astype(np.float64), res.min_env_dist, res.collision.astype(np.float64),
+                                  (np.asarray(res.qp_status) != 0).sum(axis=1).astype(np.float64)], 1)
+    else:  # (a plain run launches nothing beyond its timed steps; the ranks still combine their counters)
+        local_metrics = None
     tot = np.array([qps, ipm, hl_ms, elapsed, row_it, work.get("inband_exits", 0), B,
                     work.get("inband_beyond_clarabel_tol", 0)], dtype=np.float64)
     if comm is not None:
-        sums, maxs, all_metrics = combine_ranks(comm, tot, local_metrics)
+        if local_metrics is None:
+            from distributed_aerial_transportation_amd.sharding import reduce_values
+
+            sums, maxs, all_metrics = reduce_values(tot, "sum", comm), reduce_values(tot, "max", comm), None
+        else:
+            sums, maxs, all_metrics = combine_ranks(comm, tot, local_metrics)
         qps_all, ipm_all, row_all = float(sums[0]), float(sums[1]), float(sums[4])
         inband_all, scen_all, loose_all = int(sums[5]), int(sums[6]), int(sums[7])
         elapsed = float(maxs[3])
@@ -537,7 +588,7 @@ def main():
         qps_all, ipm_all, row_all, hl_ms_rank0 = float(qps), float(ipm), float(row_it), float(hl_ms)
         inband_all, scen_all, loose_all = int(tot[5]), B, int(tot[7])
     sust = None
-    if args.sustained_steps > 0 and not args.selftest:
+    if args.full and args.sustained_steps > 0 and not args.selftest:
         sust = sustained_loop(eng, states, args.sustained_steps, args.sustained_block, barrier, comm, n, scen_all)
     if rank != 0:
         if comm is not None:
@@ -608,8 +659,10 @@ def main():
                    "sub_batches": args.sub_batches, "persistent_blocks": args.persistent_blocks or "default"},
         "stats": {"agent_qp_solves": qps_all, "ipm_iters": ipm_all, "mean_ipm_iters_per_qp": ipm_all / max(qps_all, 1),
                   "mean_active_rows": row_all / max(ipm_all, 1),
-                  "mean_admm_iters": float(np.mean(all_metrics[:, 0])), "collisions_last_step": int(all_metrics[:, 2].sum()),
-                  "non_optimal_agent_qps_last_step": int(all_metrics[:, 3].sum()),
+                  # (the metrics step after the timed steps: --full)
+                  "mean_admm_iters": None if all_metrics is None else float(np.mean(all_metrics[:, 0])),
+                  "collisions_last_step": None if all_metrics is None else int(all_metrics[:, 2].sum()),
+                  "non_optimal_agent_qps_last_step": None if all_metrics is None else int(all_metrics[:, 3].sum()),
                   "hl_kernel_ms_per_step": launch_ms, "env_classes": classes,
                   # agent QPs accepted through the best in-band iterate, and those beyond Clarabel's
                   # 1e-8 tolerance (dat_get_inband_exits)
@@ -627,7 +680,7 @@ def main():
                      "flops_per_launch": flops_launch, "flop_model": model_string(args.mode)},
     }
     # (the CPU restatement solves at the default 1e-10: no work-matched baseline at another --qp-tol)
-    if not args.no_cpu_baseline and world == 1 and not args.selftest and args.qp_tol == 1e-10:
+    if args.full and not args.no_cpu_baseline and world == 1 and not args.selftest and args.qp_tol == 1e-10:
         out["cpu_baseline"] = cpu_baseline(n, args.cpu_sample_s, args.start, args.forests, args.warmup, args.steps, B,
                                            args.sustained_steps, args.sustained_block)
     print(json.dumps(out), flush=True)
@@ -657,12 +710,19 @@ def qp_level(args, comm, rank: int, world: int, local: int):
     accs = [L.f64(a) for a in accs]
     lib, h = eng._lib, eng._h
 
-    def step(k):
-        L.check(lib.dat_control_step(h, None, L.ptr(accs[k % ACC_POOL]), None, None, None, None, None, None))
+    # --dump-outputs: the last timed step (the fused call) hands its outputs back like a caller's control()
+    dump = None
+    if args.dump_outputs:
+        dump = (np.zeros((B, 3 * n)), np.zeros(B, dtype=np.int32), np.zeros((B, n), dtype=np.int32))
 
-    def fused(k0, K):
+    def step(k, out=None):
+        f, it, qs = (None, None, None) if out is None else (L.ptr(out[0]), L.ptr(out[1], L.I), L.ptr(out[2], L.I))
+        L.check(lib.dat_control_step(h, None, L.ptr(accs[k % ACC_POOL]), f, it, qs, None, None, None))
+
+    def fused(k0, K, out=None):
         seq = L.f64(np.stack([accs[(k0 + k) % ACC_POOL] for k in range(K)]))
-        L.check(lib.dat_control_steps(h, K, L.ptr(seq), None, None, None))
+        f, it, qs = (None, None, None) if out is None else (L.ptr(out[0]), L.ptr(out[1], L.I), L.ptr(out[2], L.I))
+        L.check(lib.dat_control_steps(h, K, L.ptr(seq), f, it, qs))
 
     if args.fused and args.mode == "centralized":
         sys.exit("bench.py: --fused covers the C-ADMM / DD configs")
@@ -684,12 +744,12 @@ def qp_level(args, comm, rank: int, world: int, local: int):
     per_step = np.full(args.steps, np.nan)
     t0 = time.perf_counter()
     if args.fused:  # (the K x B x 6 host-to-device copy of the acc sequence is inside the timed region)
-        fused(args.warmup, args.steps)
+        fused(args.warmup, args.steps, dump)
         eng.synchronize()
     else:
         for k in range(args.steps):
             ts = time.perf_counter()
-            step(args.warmup + k)
+            step(args.warmup + k, dump if k == args.steps - 1 else None)
             eng.synchronize()
             per_step[k] = (time.perf_counter() - ts) * 1e3
     t1 = time.perf_counter()
@@ -697,13 +757,23 @@ def qp_level(args, comm, rank: int, world: int, local: int):
     elapsed = t1 - t0
     w = eng.work()
     kms = eng.kernel_ms()  # k_cadmm / k_dd of the timed steps (before the metrics-only step below)
-    res = eng.control(None, L.f64(accs[0]))  # metrics only (outside the timed region)
-    # per scenario: outer iterations, min env distance, collision flag, agent QPs not OPTIMAL
-    local_metrics = np.stack([res.iters.astype(np.float64), res.min_env_dist, res.collision.astype(np.float64),
-                              (np.asarray(res.qp_status) != 0).sum(axis=1).astype(np.float64)], 1)
+    if dump is not None:
+        dump_outputs(args.dump_outputs, {"f_des": dump[0].reshape(B, n, 3).transpose(0, 2, 1), "iters": dump[1],
+                                         "qp_status": dump[2]}, rank, world)
+    local_metrics = None
+    if args.full:
+        res = eng.control(None, L.f64(accs[0]))  # metrics only (outside the timed region)
+        # per scenario: outer iterations, min env distance, collision flag, agent QPs not OPTIMAL
+        local_metrics = np.stack([res.iters.astype(np.float64), res.min_env_dist, res.collision.astype(np.float64),
+                                  (np.asarray(res.qp_status) != 0).sum(axis=1).astype(np.float64)], 1)
     tot = np.array([w["qp_solves"], w["ipm_iters"], w["hl_kernel_ms"], elapsed, w["ipm_row_iters"]])
     if comm is not None:
-        sums, maxs, all_metrics = combine_ranks(comm, tot, local_metrics)
+        if local_metrics is None:
+            from distributed_aerial_transportation_amd.sharding import reduce_values
+
+            sums, maxs, all_metrics = reduce_values(tot, "sum", comm), reduce_values(tot, "max", comm), None
+        else:
+            sums, maxs, all_metrics = combine_ranks(comm, tot, local_metrics)
         qps, ipm, rows, elapsed = float(sums[0]), float(sums[1]), float(sums[4]), float(maxs[3])
     else:
         all_metrics = local_metrics
@@ -738,8 +808,10 @@ def qp_level(args, comm, rank: int, world: int, local: int):
         "config": {"workload": workload, "n": n, "scenarios_per_gpu": B, "qp_tol": args.qp_tol,
                    "parallelism": f"scenario-sharded x{world}", "persistent_blocks": args.persistent_blocks or "default"},
         "stats": {"agent_qp_solves": qps, "ipm_iters": ipm, "mean_ipm_iters_per_qp": ipm / max(qps, 1),
-                  "mean_active_rows": rows / max(ipm, 1), "mean_admm_iters": float(np.mean(all_metrics[:, 0])),
-                  "non_optimal_agent_qps_last_step": int(all_metrics[:, 3].sum()),
+                  "mean_active_rows": rows / max(ipm, 1),
+                  # (the metrics step after the timed steps: --full)
+                  "mean_admm_iters": None if all_metrics is None else float(np.mean(all_metrics[:, 0])),
+                  "non_optimal_agent_qps_last_step": None if all_metrics is None else int(all_metrics[:, 3].sum()),
                   "kernel_ms_per_step": step_ms, "inband_exits": int(w.get("inband_exits", 0)),
                   "inband_beyond_clarabel_tol": int(w.get("inband_beyond_clarabel_tol", 0))},
         "roofline": {"bound": "fp64-valu", "achieved": tflops, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -748,7 +820,7 @@ def qp_level(args, comm, rank: int, world: int, local: int):
                      "flop_model": model_string(args.mode) + (" (DD agent QP; dual ascent not counted)"
                                                               if args.mode == "dd" else "")},
     }
-    if not args.no_cpu_baseline and world == 1 and args.qp_tol == 1e-10:
+    if args.full and not args.no_cpu_baseline and world == 1 and args.qp_tol == 1e-10:
         out["cpu_baseline"] = cpu_baseline_qp(cfg, n, args.mode, args.cpu_sample_s, args.fixed_work)
     print(json.dumps(out), flush=True)
     if comm is not None:

@@ -64,14 +64,15 @@ def test_combine_ranks_gloo_world2(tmp_path):
 
 def test_bench_spawns_ranks_selftest():
     """`python bench.py --gpus 2` without a launcher spawns two rank processes (gloo here, --selftest:
-    no solver work) that shard, combine over the process group and print ONE line from rank 0."""
+    no solver work) that shard, combine over the process group and print ONE line from rank 0 (--full: the
+    per-scenario metrics step, whose rows the ranks all-gather)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest", "--steps", "2",
-                        "--warmup", "1", "--batch", "16"], capture_output=True, text=True, timeout=240,
+                        "--warmup", "1", "--batch", "16", "--full"], capture_output=True, text=True, timeout=240,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

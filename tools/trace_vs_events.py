@@ -2,8 +2,8 @@
 
     python tools/trace_vs_events.py <run_kernel_trace.csv> <bench log> [kernel]
 
-The bench runs `warmup` launches, then the `steps` timed ones, then one metrics-only step; the timed
-launches are therefore trace launches [warmup, warmup + steps) of the kernel.
+The bench runs `warmup` launches, then the `steps` timed ones (with --full: then one metrics-only step
+and the sustained loop); the timed launches are therefore trace launches [warmup, warmup + steps) of the kernel.
 """
 import csv
 import json
