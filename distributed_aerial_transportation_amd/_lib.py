@@ -164,6 +164,8 @@ EXPORTS = {
     "dat_set_persistent_blocks": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_env_rows": (ctypes.c_int, [H, D, D, I, U8, D]),
     "dat_solve_agent_qp_batch": (ctypes.c_int, [H, ctypes.c_int, I, I, D, D, D, D, D, D, I, I, U8, D]),
+    "dat_solve_agent_qp_rows_batch": (ctypes.c_int, [H, ctypes.c_int, I, I, D, D, D, D, D, D, D, I, D, I, I, U8, D,
+                                                     U8]),
     "dat_set_low_level": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_get_kernel_ms": (ctypes.c_int, [H, D]),
     "dat_get_inband_exits": (ctypes.c_int, [H, LL, LL]),

@@ -245,11 +245,17 @@ class BatchedController:
         L.check(self._lib.dat_env_rows(self._h, L.ptr(lhs), L.ptr(rhs), L.ptr(nr, L.I), L.ptr(col, L.U8), L.ptr(md)))
         return lhs, rhs, nr, col.astype(bool), md
 
-    def solve_agent_qps(self, scenario, agent, acc_des, lam=None, rho=None, f_mean=None, c=None) -> dict:
+    def solve_agent_qps(self, scenario, agent, acc_des, lam=None, rho=None, f_mean=None, c=None, env_lhs=None,
+                        env_rhs=None, nenv=None) -> dict:
         """Raw batched agent QPs (dat_solve_agent_qp_batch): RQPPrimalSolver.solve of C-ADMM
         (control/rqp_cadmm.py:482-501; lam, f_mean (K, 3, n), rho (K,)) or DD (control/rqp_dd.py:475-505;
         c (K, 9) = (c_fi, c_Fi, c_Mi)) at the handle's current states.  Returns x ((K, 3, n) C-ADMM copies
-        f, or (K, 9) DD (f_i, F_i, M_i)), status, ipm_iters, collision, min_env_dist."""
+        f, or (K, 9) DD (f_i, F_i, M_i)), status, ipm_iters, collision, min_env_dist.
+
+        env_lhs=, env_rhs= (dat_solve_agent_qp_rows_batch): the caller's env rows lhs . dvl >= rhs instead of the
+        forest query -- K arrays (k_i, 3) and (k_i,), k_i <= 10, or compacted blocks (K, 10, 3) and (K, 10) with
+        nenv (K,).  The result then also holds certified (K,): the Farkas certificate on the dvl rows decided the
+        item (status INFEASIBLE, 0 IPM iterations); collision is False and min_env_dist +inf."""
         n = self.n
         sc, ag = L.i32(np.atleast_1d(scenario)), L.i32(np.atleast_1d(agent))
         K = sc.shape[0]
@@ -269,12 +275,36 @@ class BatchedController:
         it = np.empty(K, dtype=np.int32)
         col = np.empty(K, dtype=np.uint8)
         md = np.empty(K)
-        L.check(self._lib.dat_solve_agent_qp_batch(self._h, K, L.ptr(sc, L.I), L.ptr(ag, L.I), L.ptr(acc), L.ptr(la),
-                                                   L.ptr(rh), L.ptr(fm), L.ptr(cc), L.ptr(x), L.ptr(st, L.I),
-                                                   L.ptr(it, L.I), L.ptr(col, L.U8), L.ptr(md)))
+        cert = None
+        if env_lhs is None:
+            assert env_rhs is None and nenv is None
+            L.check(self._lib.dat_solve_agent_qp_batch(self._h, K, L.ptr(sc, L.I), L.ptr(ag, L.I), L.ptr(acc),
+                                                       L.ptr(la), L.ptr(rh), L.ptr(fm), L.ptr(cc), L.ptr(x),
+                                                       L.ptr(st, L.I), L.ptr(it, L.I), L.ptr(col, L.U8), L.ptr(md)))
+        else:
+            if nenv is None:
+                assert len(env_lhs) == K and len(env_rhs) == K
+                ne = L.i32([np.asarray(r, float).reshape(-1).shape[0] for r in env_rhs])
+                assert ne.max(initial=0) <= layout.NENV
+                el, er = np.zeros((K, layout.NENV, 3)), np.zeros((K, layout.NENV))
+                for k in range(K):
+                    el[k, :ne[k]] = np.asarray(env_lhs[k], float).reshape(ne[k], 3)
+                    er[k, :ne[k]] = np.asarray(env_rhs[k], float).reshape(ne[k])
+            else:
+                ne = L.i32(nenv).reshape(K)
+                el, er = L.f64(env_lhs).reshape(K, layout.NENV, 3), L.f64(env_rhs).reshape(K, layout.NENV)
+            cert = np.zeros(K, dtype=np.uint8)
+            L.check(self._lib.dat_solve_agent_qp_rows_batch(self._h, K, L.ptr(sc, L.I), L.ptr(ag, L.I), L.ptr(acc),
+                                                            L.ptr(la), L.ptr(rh), L.ptr(fm), L.ptr(cc), L.ptr(el),
+                                                            L.ptr(er), L.ptr(ne, L.I), L.ptr(x), L.ptr(st, L.I),
+                                                            L.ptr(it, L.I), L.ptr(col, L.U8), L.ptr(md),
+                                                            L.ptr(cert, L.U8)))
         if not dd:
             x = x.reshape(K, n, 3).transpose(0, 2, 1)
-        return {"x": x, "status": st, "ipm_iters": it, "collision": col.astype(bool), "min_env_dist": md}
+        out = {"x": x, "status": st, "ipm_iters": it, "collision": col.astype(bool), "min_env_dist": md}
+        if cert is not None:
+            out["certified"] = cert.astype(bool)
+        return out
 
     def counters(self):
         """(agent-QP solves, IPM iterations, HL steps, summed HL kernel ms) since the last reset."""

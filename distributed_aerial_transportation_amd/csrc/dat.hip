@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <mutex>
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -1829,6 +1830,10 @@ struct AgentQPArgs {
   unsigned char* col;
   double* mind;
   double* best;
+  // dat_solve_agent_qp_rows_batch: the caller's compacted env rows instead of the forest query (else null)
+  const double *elhs, *erhs;
+  const int* nenv;
+  unsigned char* cert;  // dvl_rows_infeasible returned true
 };
 
 __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
@@ -1858,9 +1863,20 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
     const double* trees;
     int nt;
     unsigned emask;
-    forest_of(a, sc, &trees, &nt);
     double lhs[DAT_NENV][3], rhs[DAT_NENV];
-    env = env_rows(prm, n, st, trees, nt, i, prm[DAT_P_AENVD], &emask, lhs, rhs);
+    if (q.elhs) {
+      // the caller's rows, compacted (slots 0 .. nenv - 1); no env query: no collision, distance +inf
+      const int ne = q.nenv[k];
+      emask = (1u << ne) - 1u;
+      for (int r = 0; r < DAT_NENV; ++r) {
+        for (int c = 0; c < 3; ++c) lhs[r][c] = r < ne ? q.elhs[((size_t)k * DAT_NENV + r) * 3 + c] : 0.0;
+        rhs[r] = r < ne ? q.erhs[(size_t)k * DAT_NENV + r] : 0.0;
+      }
+      env.min_env_dist = INFINITY;
+    } else {
+      forest_of(a, sc, &trees, &nt);
+      env = env_rows(prm, n, st, trees, nt, i, prm[DAT_P_AENVD], &emask, lhs, rhs);
+    }
     set_env_rows(P, E, S, emask, lhs, rhs);
     nr = rows_needed(P.emask);
     if (dd) {
@@ -1877,7 +1893,8 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
   const RtPtr rtr{Rt_all + 9 * i};
   double* bst = q.best + (size_t)k * best_size(1);
   // the C-ADMM agent QP as the closed loop solves it: rows certified infeasible are held (k_cadmm_tail)
-  if (!dd && !P.infeasible && dvl_rows_infeasible(shr, er, P.emask)) P.infeasible = 1;
+  const bool cert = !dd && !P.infeasible && dvl_rows_infeasible(shr, er, P.emask);
+  if (cert) P.infeasible = 1;
   IPMOut o = dd ? ipm_solve_rows<MODE_DD, 1>(nr, shr, er, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER,
                                              a.qp_tol)
                 : ipm_solve_rows<MODE_CADMM, 1, IPM_FAST_REDO>(nr, shr, er, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst,
@@ -1907,6 +1924,7 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
   q.iters[k] = o.iters;
   q.col[k] = (unsigned char)env.collision;
   q.mind[k] = env.min_env_dist;
+  q.cert[k] = (unsigned char)cert;
 }
 
 }  // namespace
@@ -2356,11 +2374,20 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
     return fail(m);
   }
   if (c.mode == DAT_MODE_CADMM) {  // the tail's workgroup may exceed the default 64 KB of dynamic LDS
+    // The limit belongs to the kernel (per device), not to the handle: it is only ever raised, so a handle
+    // of a smaller team created later never lowers it under a live handle of a larger one.
+    static std::mutex mu;
+    static int cur[64] = {0};
     const int tl = (int)cadmm_tail_lds_bytes(c.n);
-    if (hipFuncSetAttribute((const void*)k_cadmm_tail, hipFuncAttributeMaxDynamicSharedMemorySize, tl) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_cadmm0_tail, hipFuncAttributeMaxDynamicSharedMemorySize, tl) != hipSuccess) {
-      dat_destroy(h);
-      return fail("dat_create: tail kernel LDS attribute");
+    std::lock_guard<std::mutex> lk(mu);
+    int* have = c.device >= 0 && c.device < 64 ? &cur[c.device] : nullptr;
+    if (!have || tl > *have) {
+      if (hipFuncSetAttribute((const void*)k_cadmm_tail, hipFuncAttributeMaxDynamicSharedMemorySize, tl) != hipSuccess ||
+          hipFuncSetAttribute((const void*)k_cadmm0_tail, hipFuncAttributeMaxDynamicSharedMemorySize, tl) != hipSuccess) {
+        dat_destroy(h);
+        return fail("dat_create: tail kernel LDS attribute");
+      }
+      if (have) *have = tl;
     }
   }
   // LDS budgets
@@ -2829,23 +2856,30 @@ int dat_env_rows(dat_handle* h, double* lhs, double* rhs, int* nrow, unsigned ch
   return 0;
 }
 
-int dat_solve_agent_qp_batch(dat_handle* h, int count, const int* scenario, const int* agent, const double* acc_des,
-                             const double* lam, const double* rho, const double* f_mean, const double* c9, double* x,
-                             int* status, int* ipm_iters, unsigned char* collision, double* min_env_dist) {
+namespace {
+// dat_solve_agent_qp_batch (env_lhs = null: the forest query) and dat_solve_agent_qp_rows_batch (the caller's rows)
+int solve_agent_qp_batch(const char* who, dat_handle* h, int count, const int* scenario, const int* agent,
+                         const double* acc_des, const double* lam, const double* rho, const double* f_mean,
+                         const double* c9, const double* env_lhs, const double* env_rhs, const int* nenv, double* x,
+                         int* status, int* ipm_iters, unsigned char* collision, double* min_env_dist,
+                         unsigned char* certified) {
+  const std::string W = std::string(who) + ": ";
   if (!h) return fail("null handle");
-  if (count < 0) return fail("dat_solve_agent_qp_batch: negative count");
+  if (count < 0) return fail(W + "negative count");
   if (count == 0) return 0;
-  if (!h->have_params) return fail("dat_solve_agent_qp_batch: params not set");
+  if (!h->have_params) return fail(W + "params not set");
   const int mode = h->cfg.mode, n = h->cfg.n, N3 = 3 * n;
-  if (mode == DAT_MODE_CENTRALIZED) return fail("dat_solve_agent_qp_batch: C-ADMM or DD handles only");
+  if (mode == DAT_MODE_CENTRALIZED) return fail(W + "C-ADMM or DD handles only");
   const bool dd = mode == DAT_MODE_DD;
-  if (!scenario || !agent || !acc_des || !x || !status) return fail("dat_solve_agent_qp_batch: null argument");
-  if (dd ? !c9 : (!lam || !rho || !f_mean)) return fail("dat_solve_agent_qp_batch: missing multipliers");
+  if (!scenario || !agent || !acc_des || !x || !status) return fail(W + "null argument");
+  if (dd ? !c9 : (!lam || !rho || !f_mean)) return fail(W + "missing multipliers");
+  if (env_lhs && (!env_rhs || !nenv)) return fail(W + "null argument");
   for (int k = 0; k < count; ++k) {
-    if (scenario[k] < 0 || scenario[k] >= h->cfg.batch) return fail("dat_solve_agent_qp_batch: scenario out of range");
-    if (agent[k] < 0 || agent[k] >= n) return fail("dat_solve_agent_qp_batch: agent out of range");
+    if (env_lhs && (nenv[k] < 0 || nenv[k] > DAT_NENV)) return fail(W + "nenv out of range");
+    if (scenario[k] < 0 || scenario[k] >= h->cfg.batch) return fail(W + "scenario out of range");
+    if (agent[k] < 0 || agent[k] >= n) return fail(W + "agent out of range");
     if (!dd && !(rho[k] > 0.0))
-      return fail("dat_solve_agent_qp_batch: rho must be > 0 (at rho = 0 the copies f_j, j != i, are not unique)");
+      return fail(W + "rho must be > 0 (at rho = 0 the copies f_j, j != i, are not unique)");
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t C = count, nx = dd ? 9 : N3;
@@ -2870,14 +2904,20 @@ int dat_solve_agent_qp_batch(dat_handle* h, int count, const int* scenario, cons
     q.rho = (const double*)dev(sizeof(double) * C, rho);
     q.fbar = (const double*)dev(sizeof(double) * C * N3, f_mean);
   }
+  if (env_lhs) {
+    q.elhs = (const double*)dev(sizeof(double) * C * DAT_NENV * 3, env_lhs);
+    q.erhs = (const double*)dev(sizeof(double) * C * DAT_NENV, env_rhs);
+    q.nenv = (const int*)dev(sizeof(int) * C, nenv);
+  }
   q.x = (double*)dev(sizeof(double) * C * nx, nullptr);
   q.status = (int*)dev(sizeof(int) * C, nullptr);
   q.iters = (int*)dev(sizeof(int) * C, nullptr);
   q.col = (unsigned char*)dev(C, nullptr);
   q.mind = (double*)dev(sizeof(double) * C, nullptr);
   q.best = (double*)dev(sizeof(double) * C * best_size(1), nullptr);
-  bool ok = q.scen && q.agent && q.acc && q.x && q.status && q.iters && q.col && q.mind && q.best &&
-            (dd ? q.c9 != nullptr : (q.lam && q.rho && q.fbar));
+  q.cert = (unsigned char*)dev(C, nullptr);
+  bool ok = q.scen && q.agent && q.acc && q.x && q.status && q.iters && q.col && q.mind && q.best && q.cert &&
+            (dd ? q.c9 != nullptr : (q.lam && q.rho && q.fbar)) && (!env_lhs || (q.elhs && q.erhs && q.nenv));
   hipError_t e = hipSuccess;
   if (ok) {
     KArgs a = kargs(h);
@@ -2891,6 +2931,7 @@ int dat_solve_agent_qp_batch(dat_handle* h, int count, const int* scenario, cons
     if (e == hipSuccess && collision) e = hipMemcpyAsync(collision, q.col, C, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && min_env_dist)
       e = hipMemcpyAsync(min_env_dist, q.mind, sizeof(double) * C, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && certified) e = hipMemcpyAsync(certified, q.cert, C, hipMemcpyDeviceToHost, h->stream);
   }
   hipError_t es = hipStreamSynchronize(h->stream);
   if (ok && e == hipSuccess && es == hipSuccess) {
@@ -2898,10 +2939,28 @@ int dat_solve_agent_qp_batch(dat_handle* h, int count, const int* scenario, cons
     if (hipEventElapsedTime(&ms, h->e0, h->e1) == hipSuccess) h->agent_qp_ms = ms;
   }
   for (void* p : tmp) (void)hipFree(p);
-  if (!ok) return fail("dat_solve_agent_qp_batch: device allocation failed");
-  if (e != hipSuccess) return fail(std::string("dat_solve_agent_qp_batch: ") + hipGetErrorString(e));
-  if (es != hipSuccess) return fail(std::string("dat_solve_agent_qp_batch: ") + hipGetErrorString(es));
+  if (!ok) return fail(W + "device allocation failed");
+  if (e != hipSuccess) return fail(W + hipGetErrorString(e));
+  if (es != hipSuccess) return fail(W + hipGetErrorString(es));
   return 0;
+}
+}  // namespace
+
+int dat_solve_agent_qp_batch(dat_handle* h, int count, const int* scenario, const int* agent, const double* acc_des,
+                             const double* lam, const double* rho, const double* f_mean, const double* c9, double* x,
+                             int* status, int* ipm_iters, unsigned char* collision, double* min_env_dist) {
+  return solve_agent_qp_batch("dat_solve_agent_qp_batch", h, count, scenario, agent, acc_des, lam, rho, f_mean, c9,
+                              nullptr, nullptr, nullptr, x, status, ipm_iters, collision, min_env_dist, nullptr);
+}
+
+int dat_solve_agent_qp_rows_batch(dat_handle* h, int count, const int* scenario, const int* agent,
+                                  const double* acc_des, const double* lam, const double* rho, const double* f_mean,
+                                  const double* c9, const double* env_lhs, const double* env_rhs, const int* nenv,
+                                  double* x, int* status, int* ipm_iters, unsigned char* collision,
+                                  double* min_env_dist, unsigned char* certified) {
+  if (!env_lhs || !env_rhs || !nenv) return fail("dat_solve_agent_qp_rows_batch: null argument");
+  return solve_agent_qp_batch("dat_solve_agent_qp_rows_batch", h, count, scenario, agent, acc_des, lam, rho, f_mean,
+                              c9, env_lhs, env_rhs, nenv, x, status, ipm_iters, collision, min_env_dist, certified);
 }
 
 int dat_set_low_level(dat_handle* h, int kind) {

@@ -386,7 +386,10 @@ DAT_HD void set_env_rows(QPLane<NB>& P, EnvRows& E, const QPShared& S, unsigned 
 // most 4 rows, and one of at most 3 when their normals lie in a plane (the env rows of vertical trees are
 // horizontal): a Farkas certificate lambda >= 0, sum_m lambda_m a_m = 0, sum_m lambda_m b_m < 0, with lambda the
 // signed cofactors of the subsystem -- two antiparallel normals, three coplanar ones (scalar cross products in
-// their plane) or four that positively span R^3 (3 x 3 determinants).  Only strict certificates count: lambda of
+// their plane) or four that positively span R^3 (3 x 3 determinants).  Degenerate subsystems are skipped, by the
+// same 1e-9 of the normals' scale: a triple with a parallel pair, a 4-set with a coplanar triple (their cofactors
+// are rounding remnants, nonzero under fused multiply-adds; what they could certify a smaller subsystem does).
+// Only strict certificates count: lambda of
 // one sign with every entry above 1e-9 of their sum, and a violation beyond 1e-6 of the rows' scale; anything
 // closer is left to the IPM, so a certified QP is one whose residuals the IPM cannot bring into band either, and
 // one Clarabel reports infeasible (the reference then holds the previous solution, control/rqp_cadmm.py:496-499).
@@ -446,7 +449,11 @@ DAT_HD bool dvl_rows_infeasible(const SH& sh, const ER& er, unsigned emask) {
         cross3(a2, a3, c23);
         cross3(a3, a1, c31);
         const double l4 = -dot3(c12, a3);  // -det(a1, a2, a3)
-        if (fabs(l4) <= 1e-9 * n1 * n2 * n3) {  // coplanar triple: scalar cross products in the plane
+        const bool flat = fabs(l4) <= 1e-9 * n1 * n2 * n3;
+        // a triple with a (anti)parallel pair has no plane of its own: its cross products are rounding remnants
+        // (the pair itself is visited above)
+        if (flat && nc12 > 1e-9 * n1 * n2 && nrm(c23) > 1e-9 * n2 * n3 && nrm(c31) > 1e-9 * n3 * n1) {
+          // coplanar triple: scalar cross products in the plane
           const double* nv = c12;
           if (nrm(c23) > nrm(nv)) nv = c23;
           if (nrm(c31) > nrm(nv)) nv = c31;
@@ -459,9 +466,15 @@ DAT_HD bool dvl_rows_infeasible(const SH& sh, const ER& er, unsigned emask) {
           double a4[3], b4, c34[3];
           row(l, a4, b4);
           cross3(a3, a4, c34);
+          const double n4 = nrm(a4);
           const double lam[4] = {dot3(a2, c34), -dot3(a1, c34), dot3(c12, a4), l4}, bb[4] = {b1, b2, b3, b4},
-                       na[4] = {n1, n2, n3, nrm(a4)};
-          inf = inf || cert(4, lam, bb, na);
+                       na[4] = {n1, n2, n3, n4};
+          // a 4-set with a coplanar triple spans no simplex: the certificate, if any, is that triple's (visited
+          // above), and when every triple is coplanar (rank <= 2) all four cofactors are rounding remnants of
+          // no fixed sign -- the 1e-9 test relative to their own sum would pass them
+          const bool simplex = !flat && fabs(lam[0]) > 1e-9 * n2 * n3 * n4 && fabs(lam[1]) > 1e-9 * n1 * n3 * n4 &&
+                               fabs(lam[2]) > 1e-9 * n1 * n2 * n4;
+          inf = inf || (simplex && cert(4, lam, bb, na));
         }
       }
     }

@@ -244,6 +244,22 @@ int dat_solve_agent_qp_batch(dat_handle* h, int count, const int* scenario, cons
                              const double* lam, const double* rho, const double* f_mean, const double* c9, double* x,
                              int* status, int* ipm_iters, unsigned char* collision, double* min_env_dist);
 
+/* dat_solve_agent_qp_rows_batch: dat_solve_agent_qp_batch with the caller's env CBF rows in place of the forest
+ * query (_set_collision_avoidance_cbf_parameters, control/rqp_cadmm.py:307-373, is skipped for these items; the
+ * handle's forests are not read).  Item k carries nenv[k] (0..DAT_NENV = 10) rows, compacted to the front of
+ * env_lhs[30k ..] (10 x 3) and env_rhs[10k ..]; row j means env_lhs[j] . dvl >= env_rhs[j], the convention of
+ * dat_env_rows.  The same kernel and arithmetic as dat_solve_agent_qp_batch from the rows on.  No env query is
+ * made, so collision[k] = 0 and min_env_dist[k] = +inf.  certified[k] (may be NULL) is 1 exactly when the Farkas
+ * certificate on the dvl rows (dvl_rows_infeasible: env rows and the |vl| base row) decided the item, which then
+ * returns DAT_QP_INFEASIBLE with 0 IPM iterations; DAT_QP_INFEASIBLE with certified[k] = 0 comes from a zero row
+ * with a positive right-hand side or a vanishing base row.  DD handles take the rows and never set certified
+ * (no certificate on that path).  Replaces no reference call: tests of the certificate on chosen row sets. */
+int dat_solve_agent_qp_rows_batch(dat_handle* h, int count, const int* scenario, const int* agent,
+                                  const double* acc_des, const double* lam, const double* rho, const double* f_mean,
+                                  const double* c9, const double* env_lhs, const double* env_rhs, const int* nenv,
+                                  double* x, int* status, int* ipm_iters, unsigned char* collision,
+                                  double* min_env_dist, unsigned char* certified);
+
 /* ---- metric collectives of a sharded run (K8) ----------------------------------------------
  * Scenarios shard over the GPUs of a node with no collective inside the control step; what crosses GPUs is the
  * per-scenario metrics the reference's loop keeps in its lists (iteration counts, min env distance, collision
