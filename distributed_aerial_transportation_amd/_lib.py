@@ -162,6 +162,8 @@ EXPORTS = {
     "dat_reset_counters": (ctypes.c_int, [H]),
     "dat_synchronize": (ctypes.c_int, [H]),
     "dat_set_persistent_blocks": (ctypes.c_int, [H, ctypes.c_int]),
+    "dat_cadmm_slots": (ctypes.c_int, [H, ctypes.c_int, I]),
+    "dat_cadmm_row_mode": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dat_env_rows": (ctypes.c_int, [H, D, D, I, U8, D]),
     "dat_solve_agent_qp_batch": (ctypes.c_int, [H, ctypes.c_int, I, I, D, D, D, D, D, D, I, I, U8, D]),
     "dat_solve_agent_qp_rows_batch": (ctypes.c_int, [H, ctypes.c_int, I, I, D, D, D, D, D, D, D, I, D, I, I, U8, D,

@@ -135,6 +135,12 @@ class BatchedController:
         """C-ADMM / DD: resident k_cadmm / k_dd workgroups draining the scenario queues (0: default)."""
         L.check(self._lib.dat_set_persistent_blocks(self._h, int(blocks)))
 
+    def cadmm_slots(self, batch: Optional[int] = None) -> int:
+        """Scenario slots per k_cadmm wavefront for a (sub-)batch of `batch` scenarios (dat_cadmm_slots)."""
+        g = ctypes.c_int()
+        L.check(self._lib.dat_cadmm_slots(self._h, int(self.batch if batch is None else batch), ctypes.byref(g)))
+        return g.value
+
     def reset_warm_start(self) -> None:
         L.check(self._lib.dat_reset_warm_start(self._h))
 

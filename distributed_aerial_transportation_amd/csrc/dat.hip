@@ -2818,6 +2818,19 @@ int dat_set_persistent_blocks(dat_handle* h, int blocks) {
   return 0;
 }
 
+int dat_cadmm_slots(dat_handle* h, int batch, int* slots) {
+  if (!h) return fail("null handle");
+  if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_cadmm_slots: C-ADMM handles only");
+  if (batch < 1 || !slots) return fail("dat_cadmm_slots: batch must be positive and slots non-null");
+  *slots = cadmm_slots(h, batch, h->cfg.n);
+  return 0;
+}
+
+int dat_cadmm_row_mode(int n, int slots, int env_class) {
+  if (n < 1 || n > 64 || slots < 1 || slots > 64 / n || env_class < 0 || env_class >= NCLS) return -1;
+  return cadmm_row_mode(n, slots, env_class);
+}
+
 int dat_synchronize(dat_handle* h) {
   if (!h) return fail("null handle");
   HIPCHK(hipSetDevice(h->cfg.device));

@@ -942,41 +942,75 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
     }
     return (a[0] * x[0] + a[1] * x[1] + a[2] * x[2]) + b;
   };
+  // ... of a row record already in registers
+  auto rowval_r = [&](int l, const double* a, double b, const double* dv, const double* dw) -> double {
+    const double* x = l < NWROW ? dw : dv;
+    return (a[0] * x[0] + a[1] * x[1] + a[2] * x[2]) + b;
+  };
+  // lin / adj read Bv and JTi together, before the first product: one wait for the two records
   auto lin = [&](const double* u, double* dv, double* dw) {
     const auto& S = sh.get();
+    double Bv[10], JTi[10];
+    ldn<10>(&S.Bv[0], Bv);
+    ldn<10>(&S.JTi[0], JTi);
     double t[3];
-    mv3(S.Bv, u + 3, t);
+    mv3(Bv, u + 3, t);
     dv[0] = im * u[0] + t[0]; dv[1] = im * u[1] + t[1]; dv[2] = im * u[2] + t[2];
-    mv3(S.JTi, u + 3, dw);
+    mv3(JTi, u + 3, dw);
   };
   auto adj = [&](const double* gv, const double* gw, double* o) {
     const auto& S = sh.get();
+    double Bv[10], JTi[10];
+    ldn<10>(&S.Bv[0], Bv);
+    ldn<10>(&S.JTi[0], JTi);
     double t[3], s[3];
-    mtv3(S.Bv, gv, t);
-    mtv3(S.JTi, gw, s);
+    mtv3(Bv, gv, t);
+    mtv3(JTi, gw, s);
     o[0] = im * gv[0]; o[1] = im * gv[1]; o[2] = im * gv[2];
     o[3] = t[0] + s[0]; o[4] = t[1] + s[1]; o[5] = t[2] + s[2];
   };
-  auto rows_adj = [&](auto zz, double* o) {  // o = A' zz (u-space); zz(l): row multiplier
-    double gv[3] = {0, 0, 0}, gw[3] = {0, 0, 0};
+  // Row loops, one slot ahead ("How the IPM reads LDS"): slot l + 1's records are read before slot l is computed,
+  // so a row's LDS round trip overlaps the previous row's arithmetic.  The look-ahead ends at NR - 1 at compile
+  // time (nothing is read past the last slot), and a body that writes slot l's state (set_sz, ZW) does so after
+  // slot l + 1 -- another slot -- was read: no read is moved across a write to its own slot.
+  struct RowAB { double a[3], b; };          // coefficients and constant of a row
+  struct RowRec { double s, z, a[3], b; };   // ... with its (s, z) pair
+  auto for_rows_ab = [&](auto f) {
+    RowAB nx;
+    rowld(0, nx.a, nx.b);
 #pragma unroll
     for (int l = 0; l < NR; ++l) {
+      const RowAB cu = nx;
+      if (l + 1 < NR) rowld(l + 1 < NR ? l + 1 : 0, nx.a, nx.b);
+      f(l, cu);
+    }
+  };
+  auto rows_adj = [&](auto zz, double* o) {  // o = A' zz (u-space); zz(l): row multiplier
+    double gv[3] = {0, 0, 0}, gw[3] = {0, 0, 0};
+    for_rows_ab([&](int l, const RowAB& r) {
       double* g = l < NWROW ? gw : gv;
       const double zv = zz(l);
-      double a[3];
-      ra3(l, a);
+      const double* a = r.a;
       g[0] += zv * a[0]; g[1] += zv * a[1]; g[2] += zv * a[2];
-    }
+    });
     adj(gv, gw, o);
   };
-  // K_{-i} v = K v - U_i (U_i' v)
-  auto Kmul = [&](const double* v, double* o) {
-    spmv6(sh.get().K, v, o);
+  // K_{-i} v = K v - U_i (U_i' v), from records already in registers (K: 22 doubles, Rt0: the U-map of block 0):
+  // a phase reads K and the U-map once, together with what else it needs, and applies them from there
+  auto KmulR = [&](const double* K, const double* Rt0, const double* v, double* o) {
+    spmv6(K, v, o);
     double t[3], t6[6];
-    Ut_apply(rt.get(0), v, t);
-    U_apply(rt.get(0), t, t6);
+    Ut_apply(Rt0, v, t);
+    U_apply(Rt0, t, t6);
 #pragma unroll
     for (int r = 0; r < 6; ++r) o[r] -= t6[r];
+  };
+  // ... reading both records first: their reads are in flight together, one wait for the product
+  auto Kmul = [&](const double* v, double* o) {
+    double K[22], Rt0[9];
+    ldn<22>(&sh.get().K[0], K);
+    ldn<9>(rt.get(0), Rt0);
+    KmulR(K, Rt0, v, o);
   };
   auto Gy = [&](const double* yy, double* o) {
     o[0] = -yy[2]; o[1] = -sec * yy[2]; o[2] = -yy[0]; o[3] = -yy[1]; o[4] = -yy[2];
@@ -993,6 +1027,21 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
   typename RW::template Store<NR, NX> rst(rw);  // row slacks / duals / Newton row terms (registers or LDS)
   auto SL = [&](int l) -> decltype(auto) { return rst.s(l); };
   auto ZL = [&](int l) -> decltype(auto) { return rst.z(l); };
+  // the row loop one slot ahead (for_rows_ab), with the row's (s, z) pair
+  auto for_rows = [&](auto f) {
+    RowRec nx;
+    rst.sz(0, nx.s, nx.z);
+    rowld(0, nx.a, nx.b);
+#pragma unroll
+    for (int l = 0; l < NR; ++l) {
+      const RowRec cu = nx;
+      if (l + 1 < NR) {
+        rst.sz(l + 1 < NR ? l + 1 : 0, nx.s, nx.z);
+        rowld(l + 1 < NR ? l + 1 : 0, nx.a, nx.b);
+      }
+      f(l, cu);
+    }
+  };
   // per-iteration quantities: registers, or the store's aux slots (AUXM)
   double nh_r = 0.0, nq_r = 0.0, bm_r = 0.0, bk_r = 0.0;
   double rk_r[(AUXM & AUX_RES) ? 1 : 3 * NB], rf_r[(AUXM & AUX_RES) ? 1 : 6];
@@ -1295,15 +1344,13 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
           chk += Rf[r];
         }
       }
-#pragma unroll
-      for (int l = 0; l < NR; ++l) {
-        double sl, zl;
-        rst.sz(l, sl, zl);
-        const double rl = sl - (rowval(l, dv, dw));
+      for_rows([&](int l, const RowRec& r) {
+        const double sl = r.s, zl = r.z;
+        const double rl = sl - (rowval_r(l, r.a, r.b, dv, dw));
         pres = fmax(pres, fabs(rl));
         chk += rl;
         gap += sl * zl;
-      }
+      });
       out.iters = it;
       if (!(fabs(chk + gap) < 1e300)) {  // NaN or Inf anywhere in the residuals
         // at the initial point: the problem data itself is not finite (the solver-exception
@@ -1491,14 +1538,11 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
       // M = C + sum_l (z/s) a_l a_l' (u-space, packed), assembled in (dvl, dwl) coordinates
       {
         double Xv[6] = {0, 0, 0, 0, 0, 0}, Xw[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int l = 0; l < NR; ++l) {
-          double sl, zl;
-          rst.sz(l, sl, zl);
+        for_rows([&](int l, const RowRec& rr) {
+          const double sl = rr.s, zl = rr.z;
           double wgt = zl * frcp(sl);
           DAT_STAT_W(act(l) * wgt);
-          double a3v[3];
-          ra3(l, a3v);
+          const double* a3v = rr.a;
           if (ROB && act(l) > 0.0 && wgt > IPM_STIFF_W && __builtin_popcount(smask) < IPM_NSTIFF) {
             double* r = srec + __builtin_popcount(smask) * STIFF_ROW;
             r[0] = a3v[0]; r[1] = a3v[1]; r[2] = a3v[2];
@@ -1511,12 +1555,14 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
           const double a0 = a3v[0], a1 = a3v[1], a2 = a3v[2];
           X[0] += wgt * a0 * a0; X[1] += wgt * a0 * a1; X[2] += wgt * a0 * a2;
           X[3] += wgt * a1 * a1; X[4] += wgt * a1 * a2; X[5] += wgt * a2 * a2;
-        }
+        });
         // Av = [im I, Bv];  Av' Xv Av = [[im^2 Xv, im Xv Bv], [., Bv' Xv Bv]];  Aw = [0, JTi]
+        // (Bv, JTi and C are read together: one wait for the three records)
         const auto& S = sh.get();
-        double XB[9], XJ[9], Bv[10], JTi[10];
+        double XB[9], XJ[9], Bv[10], JTi[10], C[22];
         ldn<10>(S.Bv, Bv);
         ldn<10>(S.JTi, JTi);
+        ldn<22>(&S.C[var][0], C);
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -1524,8 +1570,6 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
             XB[3 * r + c] = Xv[sp3(r, 0)] * Bv[c] + Xv[sp3(r, 1)] * Bv[3 + c] + Xv[sp3(r, 2)] * Bv[6 + c];
             XJ[3 * r + c] = Xw[sp3(r, 0)] * JTi[c] + Xw[sp3(r, 1)] * JTi[3 + c] + Xw[sp3(r, 2)] * JTi[6 + c];
           }
-        double C[22];
-        ldn<22>(&S.C[var][0], C);
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -1553,18 +1597,18 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
         // T = sum_k U_k D_k^-1 U_k' (+ K_{-i} / rho)
         double T[21];
         if (MODE == MODE_CADMM) {
-          double K[22];
+          double K[22], Rd[6], Dm[6], Rt0[9];  // (K, the cone factor and the U-map: read together)
           ldn<22>(&sh.get().K[0], K);
+          dinv(0, Rd);
+          ldn<9>(rt.get(0), Rt0);
 #pragma unroll
           for (int k = 0; k < 21; ++k) T[k] = K[k] * irho;
           // K_{-i}/rho + U_i Dinv U_i' = K/rho + U_i (Dinv - I/rho) U_i'
-          double Rd[6], Dm[6];
-          dinv(0, Rd);
           dinv_explicit(Rd, Dm);
           Dm[0] -= irho;
           Dm[3] -= irho;
           Dm[5] -= irho;
-          add_UDUt(T, rt.get(0), Dm, 1.0);
+          add_UDUt(T, Rt0, Dm, 1.0);
         } else {
 #pragma unroll
           for (int k = 0; k < 21; ++k) T[k] = 0.0;
@@ -1598,6 +1642,15 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
     auto core = [&](const double bk[NB][3], const double* Rfr, const double* bu, bool has_bu, bool acc,
                     double dyo[NB][3], double* dwo, double* duo) {
       double dyn[NB][3], dwn[6], dun[6];
+      // the blocks' U-maps and cone factors, and (C-ADMM) the aggregate K: read once, first, so that the reads
+      // are in flight together; the products below take the records from registers ("How the IPM reads LDS")
+      double Rtk[NB][9], Rdk[NB][6], Kc[22];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        ldn<9>(rt.get(k), Rtk[k]);
+        dinv(k, Rdk[k]);
+      }
+      if (MODE == MODE_CADMM) ldn<22>(&sh.get().K[0], Kc);
       if (MODE == MODE_DD) {
 #pragma unroll
         for (int r = 0; r < 6; ++r) dun[r] = -Rfr[r] + (has_bu ? bu[r] : 0.0);
@@ -1605,19 +1658,17 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
           double t[3], v[3];
-          Ut_apply(rt.get(k), Rfr, t);
+          Ut_apply(Rtk[k], Rfr, t);
 #pragma unroll
           for (int c = 0; c < 3; ++c) v[c] = bk[k][c] + t[c];
-          double Rd[6];
-          dinv(k, Rd);
-          dsolve3(Rd, v, dyn[k]);
+          dsolve3(Rdk[k], v, dyn[k]);
         }
 #pragma unroll
         for (int r = 0; r < 6; ++r) dwn[r] = dun[r];
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
           double t[6];
-          U_apply(rt.get(k), dyn[k], t);
+          U_apply(Rtk[k], dyn[k], t);
 #pragma unroll
           for (int r = 0; r < 6; ++r) dwn[r] -= t[r];
         }
@@ -1626,13 +1677,11 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
           double t[3] = {0, 0, 0}, v[3], ut[6];
-          if (has_bu) Ut_apply(rt.get(k), bu, t);
+          if (has_bu) Ut_apply(Rtk[k], bu, t);
 #pragma unroll
           for (int c = 0; c < 3; ++c) bk2[k][c] = bk[k][c] + t[c];
-          double Rd[6];
-          dinv(k, Rd);
-          dsolve3(Rd, bk2[k], v);
-          U_apply(rt.get(k), v, ut);
+          dsolve3(Rdk[k], bk2[k], v);
+          U_apply(Rtk[k], v, ut);
 #pragma unroll
           for (int r = 0; r < 6; ++r) yv[r] += ut[r];
         }
@@ -1641,7 +1690,7 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
           for (int r = 0; r < 6; ++r) yv[r] = grp.sum(yv[r]);
         }
         if (MODE == MODE_CADMM) {
-          if (has_bu) Kmul(bu, g6);
+          if (has_bu) KmulR(Kc, Rtk[0], bu, g6);
 #pragma unroll
           for (int r = 0; r < 6; ++r) {
             g6[r] -= Rfr[r];  // g6 = -Rf + K_{-i} bu
@@ -1654,16 +1703,14 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
           double t[3], v[3];
-          Ut_apply(rt.get(k), tau, t);
+          Ut_apply(Rtk[k], tau, t);
 #pragma unroll
           for (int c = 0; c < 3; ++c) v[c] = bk2[k][c] - t[c];
-          double Rd[6];
-          dinv(k, Rd);
-          dsolve3(Rd, v, dyn[k]);
+          dsolve3(Rdk[k], v, dyn[k]);
         }
         if (MODE == MODE_CADMM) {
           double kt[6];
-          Kmul(tau, kt);
+          KmulR(Kc, Rtk[0], tau, kt);
 #pragma unroll
           for (int r = 0; r < 6; ++r) dwn[r] = (g6[r] - kt[r]) * irho;
         } else {
@@ -1675,7 +1722,7 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
           double t[6];
-          U_apply(rt.get(k), dyn[k], t);
+          U_apply(Rtk[k], dyn[k], t);
 #pragma unroll
           for (int r = 0; r < 6; ++r) dun[r] += t[r];
         }
@@ -1774,11 +1821,9 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
         for (int c = 0; c < 3; ++c) bk[k][c] = -RK(k, c) - g3[c];
       }
       // stiff rows: right-hand sides g of their equations go to the scratch record (their zw is 0 in bu)
-#pragma unroll
-      for (int l = 0; l < NR; ++l) {
-        double sl, zl, al3[3], bl;
-        rst.sz(l, sl, zl);
-        rowld(l, al3, bl);
+      for_rows([&](int l, const RowRec& rr) {
+        const double sl = rr.s, zl = rr.z, bl = rr.b;
+        const double* al3 = rr.a;
         const double is = frcp(sl);
         const double rzl = sl - (dot3x(l, al3, dv, dw) + bl);
         const bool stf = (smask >> l) & 1u;
@@ -1793,7 +1838,7 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
         } else {
           ZW(l) = (zl * rzl - (sl * zl + cadd)) * is;
         }
-      }
+      });
       rows_adj(ZW, bu);
       if (__builtin_expect(!corr && nst > 0, 0)) {
         // the predictor's call first solves for the iteration's stiff-row columns H abar_j (bk = 0,
@@ -1890,16 +1935,14 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
         spmv6(Cp(), du, dpi);
         {
           double gv[3] = {0, 0, 0}, gw[3] = {0, 0, 0}, adz[6];
-#pragma unroll
-          for (int l = 0; l < NR; ++l) {
-            double sl, zl, a[3];
-            rst.sz(l, sl, zl);
-            ra3(l, a);
+          for_rows([&](int l, const RowRec& rr) {
+            const double sl = rr.s, zl = rr.z;
+            const double* a = rr.a;
             const bool stf = (smask >> l) & 1u;
             const double dzl = stf ? (double)ZW(l) : ZW(l) - zl * frcp(sl) * dot3x(l, a, ddv, ddw);
             double* g = l < NWROW ? gw : gv;
             g[0] += dzl * a[0]; g[1] += dzl * a[1]; g[2] += dzl * a[2];
-          }
+          });
           adj(gv, gw, adz);
 #pragma unroll
           for (int r = 0; r < 6; ++r) dpi[r] -= adz[r];
@@ -1983,10 +2026,10 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
       }
     };
     // row directions of the current Newton solution
-    // (s_l, z_l) of the row: sl, zl (one pair read by the caller)
-    auto row_dirs = [&](int l, const double* ddv, const double* ddw, double sl, double zl, double& ds, double& dz) {
-      double al3[3], bl;
-      rowld(l, al3, bl);
+    // (the row's record -- (s, z) pair, coefficients and constant -- was read by the caller's for_rows)
+    auto row_dirs = [&](int l, const double* ddv, const double* ddw, const RowRec& rr, double& ds, double& dz) {
+      const double sl = rr.s, zl = rr.z, bl = rr.b;
+      const double* al3 = rr.a;
       const double a = dot3x(l, al3, ddv, ddw);
       ds = -(sl - (dot3x(l, al3, dv, dw) + bl)) + a;
       dz = ((smask >> l) & 1u) ? (double)ZW(l) : ZW(l) - zl * frcp(sl) * a;
@@ -2012,15 +2055,13 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
         a = fmin(a, soc_step(l4, dzs_k[k] + 5));
       }
       if constexpr (GRP::on) a = grp.min(a);
-#pragma unroll
-      for (int l = 0; l < NR; ++l) {
+      for_rows([&](int l, const RowRec& rr) {
         double ds, dz;
-        double sl, zl;
-        rst.sz(l, sl, zl);
-        row_dirs(l, ddv, ddw, sl, zl, ds, dz);
+        const double sl = rr.s, zl = rr.z;
+        row_dirs(l, ddv, ddw, rr, ds, dz);
         if (ds < 0) a = fmin(a, -sl * frcp(ds));
         if (dz < 0) a = fmin(a, -zl * frcp(dz));
-      }
+      });
       return a;
     };
     auto gap_at = [&](double al, const double* ddv, const double* ddw) {
@@ -2034,14 +2075,12 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
           g += (lj + al * dss) * (lj + al * dzs_k[k][j]);
         }
       if constexpr (GRP::on) g = grp.sum(g);
-#pragma unroll
-      for (int l = 0; l < NR; ++l) {
+      for_rows([&](int l, const RowRec& rr) {
         double ds, dz;
-        double sl, zl;
-        rst.sz(l, sl, zl);
-        row_dirs(l, ddv, ddw, sl, zl, ds, dz);
+        const double sl = rr.s, zl = rr.z;
+        row_dirs(l, ddv, ddw, rr, ds, dz);
         g += (sl + al * ds) * (zl + al * dz);
-      }
+      });
       return g;
     };
 
@@ -2122,16 +2161,13 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
     }
 #pragma unroll
     for (int r = 0; r < 6; ++r) w[r] = w[r] + alpha * dwv[r];
-    {
-#pragma unroll
-      for (int l = 0; l < NR; ++l) {
-        double ds, dz;
-        double sl, zl;
-        rst.sz(l, sl, zl);
-        row_dirs(l, ddv, ddw, sl, zl, ds, dz);
-        rst.set_sz(l, sl + alpha * ds, zl + alpha * dz);
-      }
-    }
+    // (slot l + 1's pair is read before slot l's is written: another slot)
+    for_rows([&](int l, const RowRec& rr) {
+      double ds, dz;
+      const double sl = rr.s, zl = rr.z;
+      row_dirs(l, ddv, ddw, rr, ds, dz);
+      rst.set_sz(l, sl + alpha * ds, zl + alpha * dz);
+    });
   }
   DAT_PHASE(8);
   DAT_STAT(3 + (out.why < 7 ? out.why : 6));

@@ -178,6 +178,14 @@ int dat_synchronize(dat_handle* h);
  * 4 x CUs).  A scenario's arithmetic does not depend on it; tests cap it at 1-2 workgroups so that
  * scenario slots are refilled many times within one control step. */
 int dat_set_persistent_blocks(dat_handle* h, int blocks);
+/* C-ADMM launch geometry, as the launcher computes it (host only, no device work).  dat_cadmm_slots: scenario slots
+ * per k_cadmm wavefront for a (sub-)batch of `batch` scenarios of this handle (at most 64 / n; fewer when the
+ * resident workgroups would otherwise not all get a wavefront).  dat_cadmm_row_mode: where k_cadmm keeps the IPM
+ * row state of env class `env_class` at team size n and `slots` slots -- 0 registers, 1 LDS rows, 2 LDS rows and
+ * the class's auxiliary slots -- or -1 on arguments out of range.  Tests use the two to build the smallest batch
+ * that reaches every instantiation. */
+int dat_cadmm_slots(dat_handle* h, int batch, int* slots);
+int dat_cadmm_row_mode(int n, int slots, int env_class);
 /* Summed device time [ms] since the last counter reset of the main solver kernel of each control step:
  * k_cadmm (C-ADMM) or k_dd (DD; the per-scenario quasi-Newton setup k_dd_setup excluded), 0 for
  * centralized.  Both are persistent queue drains; dat_set_persistent_blocks caps their grid.  A closed
