@@ -16,7 +16,7 @@ REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "dat_cpu.hip")
 LIB = os.path.join(HERE, "libdat_cpu.so")
 CSRC = os.path.join(REPO, "distributed_aerial_transportation_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("dat_core.hpp", "dat_qp.hpp", "dat_layout.h")]
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("dat_core.hpp", "dat_qp.hpp", "dat_cadmm_step.hpp", "dat_layout.h")]
 STAMP = LIB + ".srchash"
 D = ctypes.POINTER(ctypes.c_double)
 I = ctypes.POINTER(ctypes.c_int)

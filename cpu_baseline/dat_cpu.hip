@@ -19,7 +19,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../distributed_aerial_transportation_amd/csrc/dat_qp.hpp"
+#include "../distributed_aerial_transportation_amd/csrc/dat_cadmm_step.hpp"
 
 using namespace dat;
 
@@ -68,7 +68,7 @@ void cadmm_step(Ctx& c, int sc, long long* qp, long long* ipm) {
     env_rows(prm, n, st, trees, nt, i, prm[DAT_P_AENVD], &emask, lhs, rhs);
     set_env_rows(P[i], E[i], S, emask, lhs, rhs);
     // rows certified infeasible are held (the GPU's tail certifies them once per scenario-step)
-    if (dvl_rows_infeasible(PlainRef<QPShared>{&S}, EnvPlain{&E[i]}, P[i].emask)) P[i].infeasible = 1;
+    cadmm_certify_rows(P[i], PlainRef<QPShared>{&S}, EnvPlain{&E[i]});
   }
   double* cf = c.cf.data() + (size_t)sc * n * N3;
   double* fb = c.cfbar.data() + (size_t)sc * N3;
@@ -79,20 +79,20 @@ void cadmm_step(Ctx& c, int sc, long long* qp, long long* ipm) {
   double rho = rho0;
   int it = 0;
   const int prev_it = c.iters[sc];  // the previous step's ADMM iterations
-  // the GPU's tail rule (dat_kargs.hpp, with a forest): the warm start and stall exit of pass it >= 1 when the
-  // previous step took more than TAIL_PREV passes or it >= TAIL_PASS; the passes the tail kernel runs keep the
-  // agent QPs' warm-start records (from the step's start when routed, from the first unclean pass or TAIL_PASS)
+  // the GPU's tail rule (dat_cadmm_step.hpp, with a forest): the warm start and stall exit of the passes it names;
+  // the passes the tail kernel runs keep the agent QPs' warm-start records (tail_keeps_records: from the step's
+  // start when routed, from the first unclean pass or TAIL_PASS)
   const int tprev = c.nforest > 0 ? TAIL_PREV : 1 << 30, tpass = c.nforest > 0 ? TAIL_PASS : 1 << 30;
   double wrec[NMAXC][WREC_SIZE];
   for (int i = 0; i < n; ++i) wrec[i][0] = 0.0;
-  bool in_tail = prev_it > tprev;
+  bool in_tail = tail_wedged(prev_it, tprev);
   for (;;) {
-    in_tail = in_tail || it >= tpass;
-    const bool wson = it >= 1 && (prev_it > tprev || it >= tpass);
+    in_tail = tail_keeps_records(in_tail, it, tpass);
+    const bool wson = tail_rule(it, prev_it, tprev, tpass);
     bool unclean = false;
     for (int i = 0; i < n; ++i) {
       lane_cadmm_dynamic(P[i], prm, n, i, Rt_all, lam + i * N3, fb, rho);
-      P[i].tuned = it == 0 || prev_it <= 3;  // as k_cadmm (tuned IPM start: first pass / warm regime)
+      P[i].tuned = cadmm_tuned_start(it, prev_it);  // as k_cadmm
       double y[1][3], w[6], best[best_size(1)];
       IPMOut o = ipm_solve_rows<MODE_CADMM, 1, IPM_FAST_REDO, true>(
           rows_needed(P[i].emask), PlainRef<QPShared>{&S}, EnvPlain{&E[i]}, RtPtr{Rt_all + 9 * i}, P[i], feq + 3 * i, y,
@@ -103,37 +103,16 @@ void cadmm_step(Ctx& c, int sc, long long* qp, long long* ipm) {
 #if defined(DAT_IPM_STATS)
       ++g_ith[P[i].tuned ? 1 : 0][__builtin_popcount(P[i].emask) & 7][o.iters < 31 ? o.iters : 31];
 #endif
-      double* fi = cf + i * N3;
-      if (o.status == ST_OPTIMAL) {
-        for (int j = 0; j < n; ++j) {
-          if (j == i) {
-            for (int k = 0; k < 3; ++k) fi[3 * j + k] = y[0][k];
-          } else {
-            cadmm_free_block(Rt_all + 9 * j, lam + i * N3 + 3 * j, fb + 3 * j, o.pi, rho, fi + 3 * j);
-          }
-        }
-      } else if (o.status == ST_FAILED) {
-        for (int k = 0; k < N3; ++k) fi[k] = feq[k];
-      }
+      cadmm_take_solve(o, cf + i * N3, y[0], Rt_all, 9, lam + i * N3, fb, rho, n, i, feq);
     }
     in_tail = in_tail || (unclean && c.nforest > 0);
     ++it;
     rho = std::min(rho * tau, rho_max);
-    for (int k = 0; k < N3; ++k) {
-      double s = 0.0;
-      for (int i = 0; i < n; ++i) s += cf[i * N3 + k];
-      fb[k] = s / n;
-    }
+    for (int j = 0; j < n; ++j) cadmm_mean_block(cf, n, j, fb + 3 * j);
     double res = 0.0;
-    for (int i = 0; i < n; ++i)
-      for (int r = 0; r < 3; ++r) {
-        double s = 0.0;
-        for (int j = 0; j < n; ++j) s += std::fabs(cf[i * N3 + 3 * j + r] - fb[3 * j + r]);
-        res = std::max(res, s);
-      }
+    for (int i = 0; i < n; ++i) res = std::max(res, cadmm_total_res(cf + i * N3, fb, n));
     if (res < tol || it > max_iter) break;
-    for (int i = 0; i < n; ++i)
-      for (int k = 0; k < N3; ++k) lam[i * N3 + k] += rho * (cf[i * N3 + k] - fb[k]);
+    for (int i = 0; i < n; ++i) cadmm_dual_update(lam + i * N3, cf + i * N3, fb, rho, n);
   }
   double* fd = c.fdes.data() + (size_t)sc * N3;
   for (int i = 0; i < n; ++i)

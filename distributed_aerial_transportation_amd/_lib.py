@@ -23,12 +23,12 @@ SRCS = (SRC, SRC_CENT, SRC_COMM)
 OBJ_DIR = os.path.join(PKG, "build")
 # -ffp-contract=on: multiply-adds fused within a source expression only (not across statements, which
 # depends on the inlining context): an inlined function computes the same bits at every call site and in
-# every kernel (k_cadmm / k_cadmm_rob run the same agent-QP passes, dat_qp.hpp).  C4 A/B: k_cadmm 3.53 ->
+# every kernel (k_cadmm / k_cadmm_tail run the same agent-QP passes, dat_qp.hpp).  C4 A/B: k_cadmm 3.53 ->
 # 3.55 ms per step.
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on"]
 DEPS = [SRC, SRC_CENT, SRC_COMM, os.path.join(PKG, "csrc", "dat_core.hpp"), os.path.join(PKG, "csrc", "dat_qp.hpp"),
-        os.path.join(PKG, "csrc", "dat_kargs.hpp"), os.path.join(PKG, "csrc", "dat_layout.h"),
-        os.path.join(REPO, "include", "dat.h")]
+        os.path.join(PKG, "csrc", "dat_cadmm_step.hpp"), os.path.join(PKG, "csrc", "dat_kargs.hpp"),
+        os.path.join(PKG, "csrc", "dat_layout.h"), os.path.join(REPO, "include", "dat.h")]
 
 MODE_CENTRALIZED, MODE_CADMM, MODE_DD = 0, 1, 2
 QP_OPTIMAL, QP_INACCURATE, QP_INFEASIBLE, QP_FAILED = 0, 1, 2, 3

@@ -446,7 +446,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
     // a scenario wedged in a stall (previous step > TAIL_PREV passes) goes to the tail (key NKEY + class); with
     // sub-batches it stays in k_cadmm's queue, which hands it over after its first pass (the tail rule), the
     // same arithmetic
-    a.need[sc] = a.route && a.iters[sc] > a.tail_prev ? NKEY + cls : cls * NIB + (NIB - 1 - bin);
+    a.need[sc] = a.route && tail_wedged(a.iters[sc], a.tail_prev) ? NKEY + cls : cls * NIB + (NIB - 1 - bin);
     a.col[sc] = (unsigned char)c;
     a.mind[sc] = m;
     cnum = c;
@@ -468,8 +468,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 }
 
 // Counting sort of the scenario ids by key (need[] in [0, NKEY)): list holds the ids of key 0, then
-// key 1, ...; count[c] / count[NCLS + c] = size / start of env class c (keys c NIB .. c NIB + NIB -
-// 1), count[2 NCLS + c] = 0 (queue head).  Within a class the key is the previous step's (ADMM
+// key 1, ...; count is the class table (ScountRow, dat_kargs.hpp): size / start of env class c (keys c NIB ..
+// c NIB + NIB - 1), its queue heads zeroed.  Within a class the key is the previous step's (ADMM
 // iterations, slowest agent's IPM iterations) bin, in decreasing order, so the longest scenarios are
 // claimed first.  One BUCKET_T-thread workgroup, coalesced strided reads, LDS atomics for the
 // histogram and the scatter cursors: the order within a key is not fixed, which only changes which
@@ -498,17 +498,17 @@ __global__ __launch_bounds__(BUCKET_T) void k_bucket(int B, const int* need, int
     for (int cl = 0; cl < NCLS; ++cl) {
       int sz = 0;
       for (int b = 0; b < NIB; ++b) sz += tot[cl * NIB + b];
-      count[cl] = sz;
-      count[NCLS + cl] = st;
-      count[2 * NCLS + cl] = 0;  // queue head of the class (k_cadmm)
-      count[3 * NCLS + cl] = 0;  // hand-over list of the class (k_cadmm -> k_cadmm_tail) and its head
-      count[4 * NCLS + cl] = 0;
+      count[sc_at(SC_SIZE, cl)] = sz;
+      count[sc_at(SC_START, cl)] = st;
+      count[sc_at(SC_HEAD, cl)] = 0;       // queue head of the class (k_cadmm)
+      count[sc_at(SC_HAND_SIZE, cl)] = 0;  // hand-over list of the class (k_cadmm -> k_cadmm_tail) and its head
+      count[sc_at(SC_HAND_HEAD, cl)] = 0;
       st += sz;
     }
     for (int cl = 0; cl < NCLS; ++cl) {  // the tail-routed stretches (keys NKEY + class) behind them
-      count[5 * NCLS + cl] = tot[NKEY + cl];
-      count[6 * NCLS + cl] = kstart[NKEY + cl];
-      count[7 * NCLS + cl] = 0;
+      count[sc_at(SC_TAIL_SIZE, cl)] = tot[NKEY + cl];
+      count[sc_at(SC_TAIL_START, cl)] = kstart[NKEY + cl];
+      count[sc_at(SC_TAIL_HEAD, cl)] = 0;
     }
   }
 }
@@ -521,9 +521,32 @@ struct WaveCounters {
   long long slot = 0, pass = 0;         // wave-level: sum of (max lane IPM iterations) per pass, passes
   long long cert = 0, stall = 0, warm = 0;  // k_cadmm_tail, lane-level: certified infeasible, stall exits, warm starts
 };
+// wave-uniform sum (every lane of the wavefront must execute it)
+__device__ inline unsigned long long wave_sum(long long v) {
+  unsigned long long s = (unsigned long long)v;
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  return s;
+}
+// The lane-level solve counters of a wavefront (C-ADMM drain, k_dd), one atomic each: agent-QP solves, IPM
+// iterations and x active rows to cc[0 .. 2] (the class's counters), in-band accepts and refinement work to
+// CNT_INBAND / CNT_REF.  Every lane of the wavefront must execute it.
+__device__ __forceinline__ void flush_solve_counters(const KArgs& a, unsigned long long* cc, const WaveCounters& wc) {
+  const unsigned long long q = wave_sum(wc.qp), ip = wave_sum(wc.ipm), rw = wave_sum(wc.rowit);
+  const unsigned long long ib = wave_sum(wc.inband), lo = wave_sum(wc.loose);
+  const unsigned long long rf = wave_sum(wc.refs), co = wave_sum(wc.corrs);
+  if (threadIdx.x == 0) {
+    atomicAdd(cc, q);
+    atomicAdd(cc + 1, ip);
+    atomicAdd(cc + 2, rw);
+    if (ib) atomicAdd(a.counters + CNT_INBAND, ib);
+    if (lo) atomicAdd(a.counters + CNT_INBAND + 1, lo);
+    atomicAdd(a.counters + CNT_REF, rf);
+    atomicAdd(a.counters + CNT_REF + 1, co);
+  }
+}
 
 // A persistent 64-lane block drains the queue of env class CLS (the class's stretch of the sorted
-// scenario list, claimed one scenario at a time through a.qhead[CLS]).  The block holds G scenario
+// scenario list, claimed one scenario at a time through the class's queue head).  The block holds G scenario
 // slots of n lanes; a slot whose scenario stops is refilled with the next scenario of the queue at
 // the start of the next ADMM pass, so a wavefront no longer idles until its slowest scenario of a
 // fixed group stops (SIMD occupancy: dat_get_class_occupancy).  A scenario's arithmetic does not
@@ -532,7 +555,7 @@ struct WaveCounters {
 // when it does not end cleanly (ipm_unclean).  RB = false (k_cadmm) carries only the fast solver (IPM_FAST): a
 // scenario one of whose agent QPs does not end cleanly leaves at the end of that pass's solves with a resume
 // record (rres) and goes to its class's hand-over list; so does a scenario whose next pass falls under the tail
-// rule (TAIL_PREV / TAIL_PASS, dat_kargs.hpp), at the end of the pass before it.  RB = true (k_cadmm_tail: one
+// rule (tail_rule, dat_cadmm_step.hpp), at the end of the pass before it.  RB = true (k_cadmm_tail: one
 // scenario slot per wavefront) drains the hand-over lists after k_cadmm (tmode 0), resuming each scenario in
 // the pass it left (re-solving there only the agent QPs handed over), or the scenarios k_env_class routed to the
 // tail before the step, concurrently with k_cadmm (tmode 1), and finishes their steps (and later fused steps).
@@ -559,10 +582,10 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
   const int al = RB ? i : lane;  // the lane's column in the row / env / aux images (a clone's: its agent's)
   const int lsc = ls < G ? ls : 0;
   const bool TM = RB && a.tmode == 1;  // the tail-routed stretch of slist (k_env_class), not the hand-over list
-  const int first = TM ? a.scount[6 * NCLS + CLS] : a.scount[NCLS + CLS];
-  const int cnt = TM ? a.scount[5 * NCLS + CLS] : RB ? a.scount[3 * NCLS + CLS] : a.scount[CLS];
+  const int first = a.scount[sc_at(TM ? SC_TAIL_START : SC_START, CLS)];
+  const int cnt = a.scount[sc_at(TM ? SC_TAIL_SIZE : RB ? SC_HAND_SIZE : SC_SIZE, CLS)];
   if (cnt == 0) return;
-  int* const qh = TM ? a.scount + 7 * NCLS + CLS : RB ? a.scount + 4 * NCLS + CLS : a.qhead + CLS;
+  int* const qh = a.scount + sc_at(TM ? SC_TAIL_HEAD : RB ? SC_HAND_HEAD : SC_HEAD, CLS);
   const int* const ql = (RB && !TM ? a.rlist : a.slist) + first;
   const int rmode = RB ? 3 : cadmm_row_mode(n, G, CLS);  // wave-uniform
   CadmmLds L = cadmm_carve(smem, n, G, CLS, rmode);
@@ -660,10 +683,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
         env_to_lds<NE>(L.env, al, E);  // (clones: the same values to the same column)
         // the tail certifies infeasible rows once per scenario-step (such an agent QP would run 2 x 50 IPM
         // iterations in every pass and end INACCURATE: the previous solution is held either way)
-        if (RB && !P.infeasible && dvl_rows_infeasible(shr, err, P.emask)) {
-          P.infeasible = 1;
-          wc.cert += vi == 0;
-        }
+        if (RB && cadmm_certify_rows(P, shr, err)) wc.cert += vi == 0;
       }
     }
     // ---- one ADMM pass of every occupied slot
@@ -673,12 +693,12 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     bool hand = false;  // k_cadmm: this lane's solve was not clean (ipm_unclean)
     // k_cadmm with sub-batches (no tail routing, KArgs::route): a wedged scenario leaves before its first pass, and
     // the tail runs its step from there, as it runs a routed one
-    const bool wedged = !RB && iter == 0 && prev_iter > a.tail_prev;
+    const bool wedged = !RB && iter == 0 && tail_wedged(prev_iter, a.tail_prev);
     if (active && wedged) hand = true;
     if (active && !wedged && ((rmask >> i) & 1)) {
       lane_cadmm_dynamic(P, prm, n, i, rts, lam, fb, rho, RT_STRIDE);
       DAT_PHASE(15);
-      P.tuned = iter == 0 || prev_iter <= 3;  // see ipm_solve: first pass, or the warm closed-loop regime
+      P.tuned = cadmm_tuned_start(iter, prev_iter);
       double y[1][3], w[6];
       IPMOut o;
       DAT_PHASE(10);
@@ -688,7 +708,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
       using ERT = EnvLdsN<NE>;
       if constexpr (RB) {
         // the tail rule: warm start and stall exit in pass iter (the record is kept in every pass)
-        const bool wson = iter >= 1 && (prev_iter > a.tail_prev || iter >= a.tail_pass);
+        const bool wson = tail_rule(iter, prev_iter, a.tail_prev, a.tail_pass);
         wc.warm += vi == 0 && wson && wrl[0] == 1.0;
         o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowLds, TAIL_AUXM, NoGrp, RM, true>(
             shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowLds{L.rows, al},
@@ -738,18 +758,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
       wc.rowit += (long long)(keep * o.iters) * (__builtin_popcount(S.bmask) + __builtin_popcount(P.emask));
       wc.qp += keep;
       qstat = o.status;
-      if (vi > 0) {
-      } else if (o.status == ST_OPTIMAL) {
-        for (int j = 0; j < n; ++j) {
-          if (j == i) {
-            myf[3 * j] = y[0][0]; myf[3 * j + 1] = y[0][1]; myf[3 * j + 2] = y[0][2];
-          } else {
-            cadmm_free_block(rts + RT_STRIDE * j, lam + 3 * j, fb + 3 * j, o.pi, rho, myf + 3 * j);
-          }
-        }
-      } else if (o.status == ST_FAILED) {  // solver exception -> f_eq (control/rqp_cadmm.py:491-494)
-        for (int c = 0; c < N3; ++c) myf[c] = prm[DAT_P_FEQ(n) + c];
-      }  // otherwise hold the previous solution (control/rqp_cadmm.py:496-499)
+      if (vi == 0) cadmm_take_solve(o, myf, y[0], rts, RT_STRIDE, lam, fb, rho, n, i, prm + DAT_P_FEQ(n));
     }
     DAT_PHASE(13);
     wc.slot += wave_max(it_lane);  // (the tail's passes: counted apart, CNT_TAIL)
@@ -759,10 +768,10 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     // the slot's lanes whose solve k_cadmm hands over (a ballot: the block is one wavefront)
     const unsigned long long hb = __ballot(hand);
     const int hmask = lane < NT ? (int)((hb >> (ls * n)) & ((1ull << n) - 1ull)) : 0;
-    __syncthreads();
-    if (!RB && active && hmask) {
-      // an agent QP of the pass was not clean: k_cadmm_tail resumes the scenario here (the mean of the pass's
-      // start, the statuses of the pass's other solves; multipliers and copies are in place)
+    // k_cadmm hands the slot's scenario to k_cadmm_tail, which resumes it in pass `iter` and solves there the
+    // agent QPs of `lanes`: the mean and the lanes' statuses go with it (multipliers and copies are in place), the
+    // resume record, the class's hand-over list, and the slot is freed
+    auto hand_over = [&](int lanes) __attribute__((always_inline)) {
       for (int c = 0; c < 3; ++c) a.cfbar[(size_t)sc * N3 + 3 * i + c] = fb[3 * i + c];
       a.qstatus[(size_t)sc * n + i] = qstat;
       if (i == 0) {
@@ -770,24 +779,22 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
         rr[RRES_KSTEP] = kstep;
         rr[RRES_PASS] = iter;
         rr[RRES_WMX] = L.wmx[ls];
-        rr[RRES_LANES] = hmask;
-        a.rlist[first + atomicAdd(a.scount + 3 * NCLS + CLS, 1)] = sc;
+        rr[RRES_LANES] = lanes;
+        a.rlist[first + atomicAdd(a.scount + sc_at(SC_HAND_SIZE, CLS), 1)] = sc;
         L.sid[ls] = -1;
       }
+    };
+    __syncthreads();
+    if (!RB && active && hmask) {
+      // an agent QP of the pass was not clean: the tail redoes the pass's unclean solves (the mean of the pass's
+      // start, the statuses of the pass's other solves)
+      hand_over(hmask);
       active = false;
     }
     if (active) {
       ++iter;
       rho = fmin(rho * a.tau, a.rho_max);
-      // consensus mean, summed in agent order like the reference (control/rqp_cadmm.py:591-600)
-      // agent-major: the three components of copy k read together (same per-component order)
-      double s3[3] = {0.0, 0.0, 0.0};
-      for (int k = 0; k < n; ++k) {
-        const double* ck = cfs + k * N3 + 3 * i;
-        const double c0 = ck[0], c1 = ck[1], c2 = ck[2];
-        s3[0] += c0; s3[1] += c1; s3[2] += c2;
-      }
-      for (int c = 0; c < 3; ++c) myred[c] = s3[c] / n;
+      cadmm_mean_block(cfs, n, i, myred);
     }
     __syncthreads();
     if (active && vi == 0) {
@@ -796,34 +803,9 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     __syncthreads();
     if (active) {
       if (a.use_total_res) {
-        double rmax = 0.0;
-        double s3[3] = {0.0, 0.0, 0.0};
-        for (int j = 0; j < n; ++j) {
-          const double m0 = myf[3 * j], m1 = myf[3 * j + 1], m2 = myf[3 * j + 2];
-          s3[0] += fabs(m0 - fb[3 * j]);
-          s3[1] += fabs(m1 - fb[3 * j + 1]);
-          s3[2] += fabs(m2 - fb[3 * j + 2]);
-        }
-        for (int r = 0; r < 3; ++r) rmax = fmax(rmax, s3[r]);
-        myred[6] = rmax;
+        myred[6] = cadmm_total_res(myf, fb, n);
       } else {
-        // aggregate residual (control/rqp_cadmm.py:602-621): own copy's totals of the others
-        double F[3] = {0, 0, 0}, M[3] = {0, 0, 0};
-        for (int j = 0; j < n; ++j) {
-          if (j == i) continue;
-          double m3[3];
-          mv3(rts + RT_STRIDE * j, myf + 3 * j, m3);
-          for (int c = 0; c < 3; ++c) { F[c] += myf[3 * j + c]; M[c] += m3[c]; }
-        }
-        // E_F,i = F_i - (sum_k f_app_k - f_app_i), E_M,i likewise with moments of f_app
-        for (int k = 0; k < n; ++k) {
-          if (k == i) continue;
-          const double* fk = cfs + k * N3 + 3 * k;  // f_app_k = agent k's own block
-          double m3[3];
-          mv3(rts + RT_STRIDE * k, fk, m3);
-          for (int c = 0; c < 3; ++c) { F[c] -= fk[c]; M[c] -= m3[c]; }
-        }
-        for (int c = 0; c < 3; ++c) { myred[c] = F[c]; myred[3 + c] = M[c]; }
+        cadmm_aggregate_res(cfs, myf, rts, RT_STRIDE, n, i, myred);
       }
     }
     __syncthreads();
@@ -849,23 +831,9 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     __syncthreads();
     if (active) {
       if (!L.done[ls]) {
-        if (vi == 0)
-          for (int c = 0; c < N3; ++c) lam[c] += rho * (myf[c] - fb[c]);  // control/rqp_cadmm.py:627-629
-        if (!RB && iter >= 1 && (prev_iter > a.tail_prev || iter >= a.tail_pass)) {
-          // the tail rule holds from the next pass on: k_cadmm_tail resumes the scenario there (all lanes solve;
-          // the mean of this pass goes with it, multipliers and copies are in place)
-          for (int c = 0; c < 3; ++c) a.cfbar[(size_t)sc * N3 + 3 * i + c] = fb[3 * i + c];
-          a.qstatus[(size_t)sc * n + i] = qstat;
-          if (i == 0) {
-            int* const rr = a.rres + (size_t)sc * RRES_INTS;
-            rr[RRES_KSTEP] = kstep;
-            rr[RRES_PASS] = iter;
-            rr[RRES_WMX] = L.wmx[ls];
-            rr[RRES_LANES] = -1;
-            a.rlist[first + atomicAdd(a.scount + 3 * NCLS + CLS, 1)] = sc;
-            L.sid[ls] = -1;
-          }
-        }
+        if (vi == 0) cadmm_dual_update(lam, myf, fb, rho, n);
+        // the tail rule holds from the next pass on: all lanes solve there (the mean of this pass goes with it)
+        if (!RB && tail_rule(iter, prev_iter, a.tail_prev, a.tail_pass)) hand_over(-1);
       } else {
         // the scenario stopped: write its outputs and free the slot
         if (RB && i == 0 && vi == 0) {  // a scenario-step the tail finished (and, routed before the step, apart)
@@ -905,29 +873,11 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     __syncthreads();
   }
   // work counters of this class: one atomic per wavefront
-  unsigned long long q = (unsigned long long)wc.qp, ip = (unsigned long long)wc.ipm, rw = (unsigned long long)wc.rowit;
-  unsigned long long ib = (unsigned long long)wc.inband, lo = (unsigned long long)wc.loose;
-  unsigned long long rf = (unsigned long long)wc.refs, co = (unsigned long long)wc.corrs;
-  unsigned long long ce = (unsigned long long)wc.cert, sx = (unsigned long long)wc.stall, wm = (unsigned long long)wc.warm;
-  for (int off = 32; off > 0; off >>= 1) {
-    q += __shfl_xor(q, off);
-    ip += __shfl_xor(ip, off);
-    rw += __shfl_xor(rw, off);
-    ib += __shfl_xor(ib, off);
-    lo += __shfl_xor(lo, off);
-    rf += __shfl_xor(rf, off);
-    co += __shfl_xor(co, off);
-    if (RB) {
-      ce += __shfl_xor(ce, off);
-      sx += __shfl_xor(sx, off);
-      wm += __shfl_xor(wm, off);
-    }
-  }
+  unsigned long long* const cc = a.counters + CNT_STRIDE * CLS;
+  flush_solve_counters(a, cc, wc);
+  const unsigned long long ce = RB ? wave_sum(wc.cert) : 0, sx = RB ? wave_sum(wc.stall) : 0;
+  const unsigned long long wm = RB ? wave_sum(wc.warm) : 0;
   if (lane == 0) {
-    unsigned long long* cc = a.counters + CNT_STRIDE * CLS;
-    atomicAdd(cc, q);
-    atomicAdd(cc + 1, ip);
-    atomicAdd(cc + 2, rw);
     if (RB) {  // the tail's occupancy apart from k_cadmm's class counters
       unsigned long long* ct = a.counters + CNT_TAIL;
       atomicAdd(ct, (unsigned long long)wc.pass);
@@ -939,10 +889,6 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
       atomicAdd(cc + 3, (unsigned long long)(wc.slot * NT));
       atomicAdd(cc + 4, (unsigned long long)(wc.pass * G));
     }
-    if (ib) atomicAdd(a.counters + CNT_INBAND, ib);
-    if (lo) atomicAdd(a.counters + CNT_INBAND + 1, lo);
-    atomicAdd(a.counters + CNT_REF, rf);
-    atomicAdd(a.counters + CNT_REF + 1, co);
   }
   __syncthreads();
 }
@@ -1313,7 +1259,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
   double* lF = lamF + lsc * N3;
   double* lM = lamM + lsc * N3;
   double* rts = Rts + lsc * RT_STRIDE * n;
-  const int cnt = a.scount[0], first = a.scount[NCLS];
+  const int cnt = a.scount[sc_at(SC_SIZE, 0)], first = a.scount[sc_at(SC_START, 0)];
   const LdsRef<QPShared> shr{shs, lsc};
   const EnvLds err{envs, lane};
   const RtLds rtr{Rts, (lsc * n + i) * RT_STRIDE};
@@ -1329,7 +1275,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
   int sc = -1, iter = 0, qstat = ST_OPTIMAL, col = 0;
   int kstep = 0;  // fused control steps (dat_control_steps): the slot scenario's current step
   double mdist = 0.0;
-  long long my_ipm = 0, my_qp = 0, my_rowit = 0, my_inband = 0, my_loose = 0, my_refs = 0, my_corrs = 0;
+  WaveCounters wc;
   // phase marks (DAT_PHASE_PROF builds, tools/phase_prof.py): 11 refill + fresh slot setup, 14 prices,
   // 10 ipm_solve, 9 result bookkeeping, 13 consensus error, stop test, dual ascent, outputs
   DAT_PHASE_INIT(11);
@@ -1337,7 +1283,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
     DAT_PHASE(11);
     // ---- refill empty slots from the queue
     if (lane < NT && i == 0 && sid[ls] == -1) {
-      const int q = atomicAdd(a.qhead, 1);
+      const int q = atomicAdd(a.scount + sc_at(SC_HEAD, 0), 1);
       sid[ls] = q < cnt ? a.slist[first + q] : -2;
       done[ls] = 0;
       wmx[ls] = 0;
@@ -1427,17 +1373,17 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
                                          a.qp_tol);
 #endif
       DAT_PHASE(9);
-      my_ipm += o.iters;
-      my_inband += o.inband;
-      my_loose += inband_loose(o);
-      my_refs += o.refs;
-      my_corrs += o.corrs;
+      wc.ipm += o.iters;
+      wc.inband += o.inband;
+      wc.loose += inband_loose(o);
+      wc.refs += o.refs;
+      wc.corrs += o.corrs;
       atomicMax(&wmx[ls], o.iters);
 #ifdef DAT_ITER_HIST
       atomicAdd(&g_iter_hist[o.iters < 63 ? o.iters : 63], 1ull);
 #endif
-      my_rowit += (long long)o.iters * (__builtin_popcount(S.bmask) + __builtin_popcount(P.emask));
-      ++my_qp;
+      wc.rowit += (long long)o.iters * (__builtin_popcount(S.bmask) + __builtin_popcount(P.emask));
+      ++wc.qp;
       qstat = o.status;
       if (o.status == ST_OPTIMAL) {
         for (int c = 0; c < 3; ++c) prev[c] = y[0][c];
@@ -1564,27 +1510,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
     }
     __syncthreads();
   }
-  unsigned long long q = (unsigned long long)my_qp, ip = (unsigned long long)my_ipm, rw = (unsigned long long)my_rowit;
-  unsigned long long ib = (unsigned long long)my_inband, lo = (unsigned long long)my_loose;
-  unsigned long long rf = (unsigned long long)my_refs, co = (unsigned long long)my_corrs;
-  for (int off = 32; off > 0; off >>= 1) {
-    q += __shfl_xor(q, off);
-    ip += __shfl_xor(ip, off);
-    rw += __shfl_xor(rw, off);
-    ib += __shfl_xor(ib, off);
-    lo += __shfl_xor(lo, off);
-    rf += __shfl_xor(rf, off);
-    co += __shfl_xor(co, off);
-  }
-  if (lane == 0) {
-    atomicAdd(a.counters, q);
-    atomicAdd(a.counters + 1, ip);
-    atomicAdd(a.counters + 2, rw);
-    if (ib) atomicAdd(a.counters + CNT_INBAND, ib);
-    if (lo) atomicAdd(a.counters + CNT_INBAND + 1, lo);
-    atomicAdd(a.counters + CNT_REF, rf);
-    atomicAdd(a.counters + CNT_REF + 1, co);
-  }
+  flush_solve_counters(a, a.counters, wc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1866,12 +1792,8 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
     double lhs[DAT_NENV][3], rhs[DAT_NENV];
     if (q.elhs) {
       // the caller's rows, compacted (slots 0 .. nenv - 1); no env query: no collision, distance +inf
-      const int ne = q.nenv[k];
-      emask = (1u << ne) - 1u;
-      for (int r = 0; r < DAT_NENV; ++r) {
-        for (int c = 0; c < 3; ++c) lhs[r][c] = r < ne ? q.elhs[((size_t)k * DAT_NENV + r) * 3 + c] : 0.0;
-        rhs[r] = r < ne ? q.erhs[(size_t)k * DAT_NENV + r] : 0.0;
-      }
+      emask =
+          env_slots_of_rows(q.elhs + (size_t)k * DAT_NENV * 3, q.erhs + (size_t)k * DAT_NENV, q.nenv[k], lhs, rhs);
       env.min_env_dist = INFINITY;
     } else {
       forest_of(a, sc, &trees, &nt);
@@ -1893,8 +1815,7 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
   const RtPtr rtr{Rt_all + 9 * i};
   double* bst = q.best + (size_t)k * best_size(1);
   // the C-ADMM agent QP as the closed loop solves it: rows certified infeasible are held (k_cadmm_tail)
-  const bool cert = !dd && !P.infeasible && dvl_rows_infeasible(shr, er, P.emask);
-  if (cert) P.infeasible = 1;
+  const bool cert = !dd && cadmm_certify_rows(P, shr, er);
   IPMOut o = dd ? ipm_solve_rows<MODE_DD, 1>(nr, shr, er, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER,
                                              a.qp_tol)
                 : ipm_solve_rows<MODE_CADMM, 1, IPM_FAST_REDO>(nr, shr, er, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst,
@@ -1905,15 +1826,7 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
     for (int c = 0; c < 6; ++c) xo[3 + c] = w[c];
   } else {
     double* xo = q.x + (size_t)k * N3;
-    const double rho = q.rho[k];
-    for (int j = 0; j < n; ++j) {
-      if (j == i) {
-        for (int c = 0; c < 3; ++c) xo[3 * j + c] = y[0][c];
-      } else {
-        cadmm_free_block(Rt_all + 9 * j, q.lam + (size_t)k * N3 + 3 * j, q.fbar + (size_t)k * N3 + 3 * j, o.pi, rho,
-                         xo + 3 * j);
-      }
-    }
+    cadmm_copy_of_solve(xo, y[0], o.pi, Rt_all, 9, q.lam + (size_t)k * N3, q.fbar + (size_t)k * N3, q.rho[k], n, i);
   }
   // in-band accepts (rare: per lane, no wavefront reduction)
   if (o.inband) atomicAdd(a.counters + CNT_INBAND, 1);
@@ -2069,7 +1982,6 @@ KArgs kargs(dat_handle* h) {
   a.emask = h->emask;
   a.slist = h->slist;
   a.scount = h->scount;
-  a.qhead = h->scount ? h->scount + 2 * NCLS : nullptr;
   a.rlist = h->rlist;
   a.rres = h->rres;
   a.ll_kind = h->ll_kind;
@@ -2214,7 +2126,6 @@ KArgs sub_kargs(dat_handle* h, int off, int Bs, int s) {
   a.rres += o * RRES_INTS;
   a.wrec += o * n * WREC_SIZE;
   a.scount = h->scount + SCOUNT_INTS * s;
-  a.qhead = a.scount + 2 * NCLS;
   a.erows += (size_t)4 * DAT_NENV * n * o;
   a.emask += o * n;
   return a;

@@ -2,7 +2,7 @@
 // libdat.so (dat.hip: C-ADMM, DD, rollout, C-ABI; dat_cent.hip: the centralized kernel).
 #pragma once
 
-#include "dat_qp.hpp"
+#include "dat_cadmm_step.hpp"
 
 namespace dat {
 
@@ -10,7 +10,7 @@ constexpr int NMAX = 16;        // largest team the kernels are compiled for
 constexpr int NMAX_DD = 16;     // DD: k_dd_setup<0> keeps [H | I] (2 (6n)^2 doubles) in LDS: 144 KB at n = 16
 constexpr int IPM_MAX_ITER = 50;
 constexpr double IPM_TOL = 1e-10;  // default IPM stopping tolerance (dat_set_qp_tolerance)
-// C-ADMM env classes (cadmm_block<C>): 0 no env row, then the largest per-agent env-row count of the
+// C-ADMM env classes (cadmm_drain<C, .>): 0 no env row, then the largest per-agent env-row count of the
 // scenario's QPs <= 2, <= 5, <= DAT_NENV.  Row slots of class C: NBASE + CLASS_ENV[C].
 constexpr int NCLS = 4;
 __host__ __device__ constexpr int class_env_rows(int c) { return c == 0 ? 0 : c == 1 ? 2 : c == 2 ? 5 : DAT_NENV; }
@@ -48,16 +48,25 @@ constexpr int CNT_ROB = CNT_REF + 2;
 // (dvl_rows_infeasible, per scenario-step), [4] stall exits, [5] warm-started solves
 constexpr int CNT_TAIL = CNT_ROB + 1;
 // k_env_class: [0] scenario-steps with a collision flag (example/env_forest.py:158-159), [1] the smallest
-// min env distance of the counted steps (fp64 bits: atomicMin orders positive doubles)
+// min env distance of the counted steps (dist_key of the signed distance, an order-preserving integer key:
+// atomicMin orders the keys as the distances, a collided payload's negative one included; dist_of_key reads it back)
 constexpr int CNT_COLL = CNT_TAIL + 6;
 constexpr int DAT_NCOUNTERS = CNT_COLL + 2;
-// class table of the C-ADMM / DD queues (k_bucket), per sub-batch: [0, NCLS) class sizes, [NCLS, 2 NCLS) class
-// starts in slist, [2 NCLS, 3 NCLS) queue heads; C-ADMM robust redo: [3 NCLS, 4 NCLS) sizes of the classes'
-// robust lists (rlist, same class starts), [4 NCLS, 5 NCLS) their queue heads
-// [5 NCLS, 6 NCLS) sizes of the classes' tail-routed stretches of slist (keys NKEY + class), [6 NCLS, 7 NCLS)
-// their starts, [7 NCLS, 8 NCLS) their heads
-constexpr int SCOUNT_INTS = 8 * NCLS;
-// Resume record of a scenario k_cadmm hands to k_cadmm_rob: the fused control step and the ADMM pass it
+// Class table of the C-ADMM / DD queues (scount, filled by k_bucket), per sub-batch: SC_ROWS rows of NCLS ints
+enum ScountRow {
+  SC_SIZE,        // class sizes
+  SC_START,       // class starts in slist (and in rlist: the hand-over lists share them)
+  SC_HEAD,        // queue heads of the classes (k_cadmm / k_dd claim through them)
+  SC_HAND_SIZE,   // sizes of the classes' hand-over lists (rlist: k_cadmm appends, k_cadmm_tail drains)
+  SC_HAND_HEAD,   // their queue heads
+  SC_TAIL_SIZE,   // sizes of the classes' tail-routed stretches of slist (keys NKEY + class)
+  SC_TAIL_START,  // their starts
+  SC_TAIL_HEAD,   // their queue heads
+  SC_ROWS
+};
+constexpr int SCOUNT_INTS = SC_ROWS * NCLS;
+__host__ __device__ constexpr int sc_at(ScountRow row, int cls) { return row * NCLS + cls; }
+// Resume record of a scenario k_cadmm hands to k_cadmm_tail: the fused control step and the ADMM pass it
 // stopped in, the IPM-iteration maximum so far, and the mask of its agent lanes whose solve of that pass
 // was not clean (the others' results of the pass stand; -1: all, a hand-over between passes by the tail rule)
 constexpr int RRES_KSTEP = 0, RRES_PASS = 1, RRES_WMX = 2, RRES_LANES = 3, RRES_INTS = 4;
@@ -91,15 +100,14 @@ struct KArgs {
   unsigned char* col;
   double* err;
   unsigned long long* counters;  // [0] agent-QP solves, [1] IPM iterations, [2] IPM iterations x active rows
-                                 // (C-ADMM: [CNT_STRIDE k + .] per env class k, cadmm_block<k>)
+                                 // (C-ADMM: [CNT_STRIDE k + .] per env class k, cadmm_drain<k, .>)
   int G;                         // C-ADMM: scenario slots per k_cadmm wavefront (cadmm_slots)
   int* need;                     // C-ADMM: per-scenario sort key of the step (k_env_class)
   int* ipmx;                     // C-ADMM: IPM iterations of the scenario's slowest agent QP, previous step
   int* slist;                    // C-ADMM: scenario ids grouped by class, then by key (k_bucket)
-  int* scount;                   // C-ADMM: [0, NCLS) class sizes, [NCLS, 2 NCLS) class start offsets
-  int* qhead;                    // C-ADMM: [NCLS] queue heads of the classes (reset by k_bucket)
-  int* rlist;                    // C-ADMM: scenarios whose step k_cadmm_rob redoes, by class (class starts as slist)
-  int* rres;                     // C-ADMM: per listed scenario, where k_cadmm_rob resumes it (RRES_* fields)
+  int* scount;                   // C-ADMM / DD: the class table of the queues (ScountRow, sc_at; reset by k_bucket)
+  int* rlist;                    // C-ADMM: scenarios whose step k_cadmm_tail finishes, by class (class starts as slist)
+  int* rres;                     // C-ADMM: per listed scenario, where k_cadmm_tail resumes it (RRES_* fields)
   double* erows;                 // C-ADMM: env rows of the step per agent (k_env_class -> k_cadmm), SoA:
                                  //   [(4 j + c) B n + sc n + i], c < 3: lhs, c = 3: rhs
   unsigned* emask;               // C-ADMM: [B n] env row mask of the step

@@ -231,6 +231,7 @@ constexpr int WREC_SIZE = 28 + 2 * DAT_MAXROW;
 // batched with.  Normal C4 steps take 1-14 passes: the warm closed loop never meets it.
 // (TAIL_PASS = 8 measured worse: the warm window's 9-14-pass scenarios then finish after k_cadmm, C4 3.87 -> 4.58
 // ms per step, and the 10 s loop did not gain, 33.0 -> 34.0 ms per step; tools/r06_ab.sh)
+// The rule as predicates (tail_rule, tail_wedged): dat_cadmm_step.hpp.
 constexpr int TAIL_PREV = 20, TAIL_PASS = 16;
 
 // ------------------------------------------------------------------ shared data
@@ -2210,13 +2211,13 @@ DAT_HD __attribute__((always_inline)) IPMOut ipm_attempt(const SH& sh, const ER&
 // lose the digits convergence needs) and is redone by the robust instantiation from scratch; the better of
 // the two outcomes is kept (ipm_rank).  A clean fast solve meets the tolerance on residuals evaluated from
 // the iterate itself, however its Newton systems were solved.
-//   IPM_FAST        fast (k_cadmm, which hands a scenario with an unclean solve to k_cadmm_rob; DD, centralized)
+//   IPM_FAST        fast (k_cadmm, which hands a scenario with an unclean solve to k_cadmm_tail; DD, centralized)
 //   IPM_ROBUST      robust
-//   IPM_FAST_REDO   the C-ADMM agent QP's definition: fast, redone robustly when not clean (k_cadmm_rob, the
+//   IPM_FAST_REDO   the C-ADMM agent QP's definition: fast, redone robustly when not clean (k_cadmm_tail, the
 //                   single-QP surfaces, host builds)
 //   IPM_FAST_R      IPM_FAST as IPM_FAST_REDO's first attempt: the same arithmetic as a template instance of
 //                   its own, so that k_cadmm's IPM_FAST instance has one call site per class and is inlined
-//                   (shared with k_cadmm_rob's redo it was called, and k_cadmm took 7 % longer)
+//                   (shared with k_cadmm_tail's redo it was called, and k_cadmm took 7 % longer)
 enum { IPM_FAST = 0, IPM_FAST_R = 1, IPM_ROBUST = 2, IPM_FAST_REDO = 3 };
 // 0 converged, 1 in-band OPTIMAL, 2 not OPTIMAL
 DAT_HD int ipm_rank(const IPMOut& r) { return r.status != ST_OPTIMAL ? 2 : r.inband ? 1 : 0; }

@@ -12,7 +12,8 @@ CORE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "distributed_aerial_
 
 
 def build(force=False):
-    deps = [SRC] + [os.path.join(CORE, f) for f in ("dat_core.hpp", "dat_qp.hpp", "dat_layout.h")]
+    deps = [SRC] + [os.path.join(CORE, f)
+                    for f in ("dat_core.hpp", "dat_qp.hpp", "dat_cadmm_step.hpp", "dat_layout.h")]
     if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950",
                                SRC, "-o", LIB])
@@ -81,6 +82,11 @@ def qp_cadmm_warm(prm, n, st, acc, lhs, rhs, i, lam, fbar, rho, wrec, wson=True,
                                     ctypes.c_double(rho), int(tuned), wrec.ctypes.data_as(D), int(bool(wson)), f.ctypes.data_as(D),
                                     ctypes.byref(it), ctypes.byref(ib))
     return f, status, it.value, ib.value
+
+
+def tail_rule(ps, prev):
+    """the tail rule names pass ps of a step whose previous step took prev passes (tail_rule, dat_cadmm_step.hpp)"""
+    return bool(lib().hs_tail_rule(int(ps), int(prev)))
 
 
 def last_stiff():

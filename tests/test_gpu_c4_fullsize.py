@@ -1,6 +1,6 @@
 """Full-size C4 (the bench's own workload): the 65,536 path-start scenarios of bench.py (n = 6
 C-ADMM, seeded forests 0..63) for 3 HL steps through the production closed loop (dat_closed_loop: device
-desired acceleration -> k_env_class -> k_cadmm / k_cadmm_rob -> 10 rollout steps), and the per-GPU shard of
+desired acceleration -> k_env_class -> k_cadmm / k_cadmm_tail -> 10 rollout steps), and the per-GPU shard of
 the 8-GPU split (8,192 scenarios) on 4 sub-batch streams as bench.py runs it (auto_sub_batches).
 
 Size-independent properties (the oracle cannot run 65,536 scenarios):

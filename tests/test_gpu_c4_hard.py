@@ -5,7 +5,7 @@ through the dual update (:627-629) and the agent QPs carry active rows and cones
 1e10-1e19.  There the round-4 solver accepted in-band iterates outside Clarabel's 1e-8 (22 and 48 over these
 two stretches on the host build) and left the oracle's f_des by 2e-4 at steps 16-17 of the second.
 
-The GPU loop (cold warm state, the production k_env_class -> k_cadmm / k_cadmm_rob path) must follow the
+The GPU loop (cold warm state, the production k_env_class -> k_cadmm / k_cadmm_tail path) must follow the
 oracle through both stretches: ADMM iteration counts exact, and f_des within 1e-5 relative at every step --
 or within the loop's own sensitivity to solver accuracy: 5 x the oracle's spread between QP tolerances 1e-10
 and 1e-11 (f_des_1e10; 1.1e-2 at step 18 of the second stretch), or the spread at Clarabel's own tolerance

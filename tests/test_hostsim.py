@@ -209,9 +209,9 @@ def test_c4_stall_stretch_matches_oracle():
             fbar = self.f_mean.T.reshape(-1).copy()
             ps = tally["pass"]
             tuned = tally["tuned"] if ps == 0 else 0
-            # the tail rule (dat_qp.hpp TAIL_PREV / TAIL_PASS): warm start + stall exit in the passes it names;
+            # the tail rule (dat_cadmm_step.hpp tail_rule): warm start + stall exit in the passes it names;
             # the passes the tail kernel runs keep the warm-start records
-            wson = ps >= 1 and (tally["prev"] > TAIL_PREV or ps >= TAIL_PASS)
+            wson = hs.tail_rule(ps, tally["prev"])
             tally["tail"] = tally["tail"] or ps >= TAIL_PASS
             rec = np.ascontiguousarray(wrec[i]) if tally["tail"] else np.zeros(hs.WREC_SIZE)
             f, status, _, inb = hs.qp_cadmm_warm(prm, n, pack_state(s_), np.concatenate(acc), env.lhs, env.rhs, i, lam,
