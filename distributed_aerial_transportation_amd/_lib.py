@@ -178,6 +178,13 @@ EXPORTS = {
     "dat_get_agent_qp_ms": (ctypes.c_int, [H, D]),
     "dat_rp_rollout": (ctypes.c_int, [H, ctypes.c_int, D]),
     "dat_low_level_control": (ctypes.c_int, [H, D, D, D]),
+    "dat_log_begin": (ctypes.c_int, [H, I, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dat_log_counts": (ctypes.c_int, [H, LL, LL, LL]),
+    "dat_log_read_hl": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int, D, I, I, D, U8, D, D, D]),
+    "dat_log_read_steps": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int, LL, D, D, D, D, D]),
+    "dat_log_read_summary": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int, I, D, U8]),
+    "dat_log_clear": (ctypes.c_int, [H]),
+    "dat_log_end": (ctypes.c_int, [H]),
     "dat_comm_unique_id": (ctypes.c_int, [U8]),
     "dat_comm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, U8, ctypes.POINTER(H)]),
     "dat_comm_destroy": (ctypes.c_int, [H]),

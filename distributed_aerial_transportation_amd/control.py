@@ -215,6 +215,77 @@ class BatchedController:
     def closed_loop(self, hl_steps: int) -> None:
         L.check(self._lib.dat_closed_loop(self._h, int(hl_steps)))
 
+    # -- the closed loop's log (dat_log_*): closed_loop records into HBM, log_read copies the records out
+    def log_begin(self, scenarios=None, log_every: Optional[int] = None, hl_capacity: int = 100,
+                  summary: bool = False) -> None:
+        """Open a log: closed_loop then keeps, for `scenarios` (strictly increasing indices; None: all, []: none),
+        an HL record per control step and a step record at every simulation step i with i % log_every == 0
+        (log_every: the reference's log_freq, default hl_every), and with summary=True the per-step iters,
+        min_env_dist and collision of all scenarios.  The buffers hold hl_capacity HL steps; a closed_loop call
+        that would pass it raises DatError (log_read, log_clear, then go on).  control, control_steps, rollout
+        and rp_rollout are not recorded."""
+        if scenarios is None:
+            sc, count = None, self.batch
+        else:
+            sc = L.i32(np.asarray(scenarios).reshape(-1))
+            count = sc.shape[0]
+        le = int(self.cfg.hl_every if log_every is None else log_every)
+        L.check(self._lib.dat_log_begin(self._h, L.ptr(sc, L.I) if count else None, count, le, int(hl_capacity),
+                                        int(summary)))
+        self._log = (np.arange(self.batch, dtype=np.int32) if sc is None else sc, bool(summary))
+
+    def log_counts(self) -> tuple:
+        """(HL records held, step records held, log clock in simulation steps) -- dat_log_counts."""
+        k, s, c = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(self._lib.dat_log_counts(self._h, ctypes.byref(k), ctypes.byref(s), ctypes.byref(c)))
+        return k.value, s.value, c.value
+
+    def log_read(self) -> dict:
+        """The records held, time-major numpy arrays (R recorded scenarios, K HL records, Ks step records):
+        scenarios (R,); HL: f_des (K, R, 3, n), iters (K, R), qp_status (K, R, n), min_env_dist (K, R), collision
+        (K, R) bool, x_ref, v_ref (K, R, 3), solve_ms (K,) (NaN with sub-batch streams); steps: step_index (Ks,),
+        thrust (Ks, R, n), moment (Ks, R, 3, n), state (Ks, R, 12n + 18), x_err, v_err (Ks, R); with the summary
+        tier: sum_iters, sum_min_env_dist, sum_collision (K, B)."""
+        if getattr(self, "_log", None) is None:
+            raise L.DatError("log_read: no log open")
+        scen, summary = self._log
+        n, B, R = self.n, self.batch, scen.shape[0]
+        K, Ks, _ = self.log_counts()
+        f = np.empty((K, R, n, 3))
+        it = np.empty((K, R), dtype=np.int32)
+        qs = np.empty((K, R, n), dtype=np.int32)
+        md = np.empty((K, R))
+        col = np.empty((K, R), dtype=np.uint8)
+        xr, vr, ms = np.empty((K, R, 3)), np.empty((K, R, 3)), np.empty(K)
+        L.check(self._lib.dat_log_read_hl(self._h, 0, K, L.ptr(f), L.ptr(it, L.I), L.ptr(qs, L.I), L.ptr(md),
+                                          L.ptr(col, L.U8), L.ptr(xr), L.ptr(vr), L.ptr(ms)))
+        si = np.empty(Ks, dtype=np.int64)
+        th, mo = np.empty((Ks, R, n)), np.empty((Ks, R, n, 3))
+        st = np.empty((Ks, R, layout.state_size(n)))
+        xe, ve = np.empty((Ks, R)), np.empty((Ks, R))
+        L.check(self._lib.dat_log_read_steps(self._h, 0, Ks, L.ptr(si, L.LL), L.ptr(th), L.ptr(mo), L.ptr(st),
+                                             L.ptr(xe), L.ptr(ve)))
+        out = {"scenarios": scen.copy(), "f_des": f.transpose(0, 1, 3, 2), "iters": it, "qp_status": qs,
+               "min_env_dist": md, "collision": col.astype(bool), "x_ref": xr, "v_ref": vr, "solve_ms": ms,
+               "step_index": si, "thrust": th, "moment": mo.transpose(0, 1, 3, 2), "state": st, "x_err": xe,
+               "v_err": ve}
+        if summary:
+            sit = np.empty((K, B), dtype=np.int32)
+            smd = np.empty((K, B))
+            sco = np.empty((K, B), dtype=np.uint8)
+            L.check(self._lib.dat_log_read_summary(self._h, 0, K, L.ptr(sit, L.I), L.ptr(smd), L.ptr(sco, L.U8)))
+            out.update(sum_iters=sit, sum_min_env_dist=smd, sum_collision=sco.astype(bool))
+        return out
+
+    def log_clear(self) -> None:
+        """Empty the log's buffers and keep its clock (dat_log_clear)."""
+        L.check(self._lib.dat_log_clear(self._h))
+
+    def log_end(self) -> None:
+        """Close the log and free its buffers (dat_log_end)."""
+        L.check(self._lib.dat_log_end(self._h))
+        self._log = None
+
     def control_steps(self, acc_seq: np.ndarray) -> StepResult:
         """dat_control_steps: acc_seq (K, B, 6) -> K fused control steps of every scenario from the resident
         states (C-ADMM / DD without a forest); the result holds the last step's outputs.  The fused path

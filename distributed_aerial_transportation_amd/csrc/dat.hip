@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <algorithm>
 #include <chrono>
@@ -1523,8 +1524,28 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
 // same trajectory).  Per-lane state is one quadrotor plus the payload (~40 doubles), so nothing
 // spills and the kernel runs many wavefronts per SIMD, for any n (k_rollout<0> kept the whole state
 // of a large team in scratch).
+//
+// LOG = true (a log is open, dat_log_begin): the launch is one HL period of dat_closed_loop and also writes the
+// period's records (layouts: dat_layout.h DAT_LOG_*).  On entry lane i of a recorded scenario writes its f_des
+// and qp_status, lane 0 the rest of the HL record from the entry state (the HL instant's); lane 0 of every
+// scenario writes the summary tier.  At a logged step lane i writes the thrust and moment it applies and, after
+// the integration (and the polar projection), its R and w; lane 0 the payload and the tracking errors.  A
+// scenario's record is contiguous and a lane's stores are runs of 4, 9 + 3 and 20 doubles, like the state
+// write-back below.  LOG = false compiles to the kernel without any of it.
 constexpr int RO_X = 6;  // per lane in LDS: u = f R e3 (3), hat(r_com) Rl' u (3)
-__global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, double dt, const double* fdes) {
+constexpr double REF_X_OFFSET = 1.5;  // x_ref leads the payload by 1.5 m (example/rqp_example.py:36)
+// the mountain record m of scenario sc's desired-acceleration law (without a forest: the flat default)
+__device__ inline void mountain_of(const KArgs& a, int sc, double* m) {
+  const int f = (a.nforest > 0) ? (a.scen_forest ? a.scen_forest[sc] : 0) : -1;
+  if (f < 0 || a.mountain == nullptr) {
+    m[DAT_M_CX] = 30.0; m[DAT_M_CY] = 0.0; m[DAT_M_RADIUS] = 25.0; m[DAT_M_SPHERE_R] = 1e300; m[DAT_M_DEPTH] = 0.0;
+  } else {
+    for (int k = 0; k < DAT_MOUNTAIN_SIZE; ++k) m[k] = a.mountain[(size_t)f * DAT_MOUNTAIN_SIZE + k];
+  }
+}
+template <bool LOG>
+__global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, double dt, const double* fdes,
+                                                       std::conditional_t<LOG, LogArgs, NoLog> lg) {
   __shared__ double xs[64 * RO_X];
   const int n = a.n, G = 64 / n, NT = G * n;
   const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
@@ -1545,6 +1566,45 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
     }
     cnt = a.counter[sc];
   }
+  // LOG: what a lane needs again at a logged step waits in LDS (its slot; lane 0 of a scenario: x_ref, v_ref of
+  // this HL period), each word read back by the lane that wrote it (no barrier needed), so the step loop carries no
+  // per-lane log state of its own; the next logged step of the launch and its record are the same for every lane
+  __shared__ int lslot[LOG ? 64 : 1];
+  __shared__ double lref[LOG ? 64 / 3 * 6 : 1];
+  [[maybe_unused]] int lnext = 0;
+  [[maybe_unused]] double* lrec = nullptr;  // slot 0 of the record of that step
+  if constexpr (LOG) {
+    const long long first = (lg.clock + lg.log_every - 1) / lg.log_every;  // first logged step / log_every
+    lnext = (int)(first * lg.log_every - lg.clock);
+    lrec = lg.step + (size_t)(first - lg.step_base) * lg.nslot * DAT_LOG_ST_WORDS(n);
+    int slot = -1;
+    if (valid) {
+      const long long hk = lg.clock / lg.hl_every - lg.hl_base;
+      if (i == 0 && lg.sum_iters) {
+        const size_t o = (size_t)hk * lg.batch + sc;
+        lg.sum_iters[o] = a.iters[sc];
+        lg.sum_mind[o] = a.mind[sc];
+        lg.sum_col[o] = a.col[sc];
+      }
+      slot = lg.slot[sc];
+      if (slot >= 0) {
+        double* r = lg.hl + ((size_t)hk * lg.nslot + slot) * DAT_LOG_HL_WORDS(n);
+        int* ri = reinterpret_cast<int*>(r + DAT_LOG_HL_INTS(n));
+        for (int c = 0; c < 3; ++c) r[3 * i + c] = fd[c];
+        ri[2 + i] = a.qstatus[(size_t)sc * n + i];
+        if (i == 0) {
+          double m[DAT_MOUNTAIN_SIZE], ref[6];  // x_ref, v_ref
+          mountain_of(a, sc, m);
+          forest_references(xl, m, REF_X_OFFSET, ref, ref + 3);
+          r[DAT_LOG_HL_MIND(n)] = a.mind[sc];
+          for (int c = 0; c < 6; ++c) r[DAT_LOG_HL_XREF(n) + c] = lref[6 * ls + c] = ref[c];
+          ri[0] = a.iters[sc];
+          ri[1] = a.col[sc];
+        }
+      }
+    }
+    lslot[lane] = slot;
+  }
   const double* J = prm + DAT_P_J(n) + 9 * i;
   const double* Ji = prm + DAT_P_JINV(n) + 9 * i;
   double* mine = xs + lane * RO_X;
@@ -1554,6 +1614,13 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
     if (valid) {
       double f, M[3], Jw[3], wJw[3], t[3];
       ll_control_agent(R, W, J, fd, &f, M, a.ll_kind);
+      if constexpr (LOG) {
+        if (s == lnext && lslot[lane] >= 0) {  // 32-byte aligned: two 16-byte stores
+          double2* w = reinterpret_cast<double2*>(lrec + (size_t)lslot[lane] * DAT_LOG_ST_WORDS(n) + 4 * i);
+          w[0] = make_double2(f, M[0]);
+          w[1] = make_double2(M[1], M[2]);
+        }
+      }
       mv3(J, W, Jw);
       cross3(W, Jw, wJw);
       for (int c = 0; c < 3; ++c) t[c] = M[c] - wJw[c];
@@ -1611,6 +1678,34 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
         polar3(R);
         cnt = 0;
       }
+      if constexpr (LOG) {
+        if (s == lnext && lslot[lane] >= 0) {
+          double* rec = lrec + (size_t)lslot[lane] * DAT_LOG_ST_WORDS(n);
+          double* q = rec + DAT_LOG_ST_STATE(n);
+          for (int k = 0; k < 9; ++k) q[DAT_S_R(n) + 9 * i + k] = R[k];
+          for (int c = 0; c < 3; ++c) q[DAT_S_W(n) + 3 * i + c] = W[c];
+          if (i == 0) {
+            const double* ref = lref + 6 * ls;
+            double ex[3], ev[3];
+            for (int c = 0; c < 3; ++c) {
+              q[DAT_S_XL(n) + c] = xl[c];
+              q[DAT_S_VL(n) + c] = vl[c];
+              q[DAT_S_WL(n) + c] = wl[c];
+              ex[c] = ref[c] - xl[c];
+              ev[c] = ref[3 + c] - vl[c];
+            }
+            for (int k = 0; k < 9; ++k) q[DAT_S_RL(n) + k] = Rl[k];
+            rec[DAT_LOG_ST_XERR(n)] = sqrt(dot3(ex, ex));
+            rec[DAT_LOG_ST_XERR(n) + 1] = sqrt(dot3(ev, ev));
+          }
+        }
+      }
+    }
+    if constexpr (LOG) {
+      if (s == lnext) {
+        lnext += lg.log_every;
+        lrec += (size_t)lg.nslot * DAT_LOG_ST_WORDS(n);
+      }
     }
     __syncthreads();  // the sums are read before the next step overwrites them
   }
@@ -1629,9 +1724,14 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
   }
 }
 
-void launch_rollout(const KArgs& a, int B, hipStream_t stream, int steps, double dt, const double* fdes) {
+// lg: the open log's arguments at this launch (dat_closed_loop), or null: the plain kernel
+void launch_rollout(const KArgs& a, int B, hipStream_t stream, int steps, double dt, const double* fdes,
+                    const LogArgs* lg = nullptr) {
   const int G = 64 / a.n;
-  hipLaunchKernelGGL(k_rollout_agents, dim3((B + G - 1) / G), dim3(64), 0, stream, a, steps, dt, fdes);
+  if (lg)
+    hipLaunchKernelGGL(k_rollout_agents<true>, dim3((B + G - 1) / G), dim3(64), 0, stream, a, steps, dt, fdes, *lg);
+  else
+    hipLaunchKernelGGL(k_rollout_agents<false>, dim3((B + G - 1) / G), dim3(64), 0, stream, a, steps, dt, fdes, NoLog{});
 }
 
 // RQPLowLevelController.control (control/rqp_centralized.py:518-535) at the current states: thrust
@@ -1643,8 +1743,9 @@ __global__ void k_low_level(KArgs a, const double* fdes, double* fo, double* Mo)
   const int sc = t / n, i = t - sc * n;
   const double* prm = prm_of(a, sc);
   const double* st = a.state + (size_t)sc * a.S;
-  ll_control_agent(st + DAT_S_R(n) + 9 * i, st + DAT_S_W(n) + 3 * i, prm + DAT_P_J(n) + 9 * i,
-                   fdes + (size_t)sc * 3 * n + 3 * i, fo + t, Mo + 3 * (size_t)t, a.ll_kind);
+  // (inlined here as in the rollout instantiations: with three callers the inliner would leave a call)
+  [[clang::always_inline]] ll_control_agent(st + DAT_S_R(n) + 9 * i, st + DAT_S_W(n) + 3 * i, prm + DAT_P_J(n) + 9 * i,
+                                            fdes + (size_t)sc * 3 * n + 3 * i, fo + t, Mo + 3 * (size_t)t, a.ll_kind);
 }
 
 // rigid payload (system/rigid_payload.py:93-130): `steps` steps of dt with the forces f held, one lane per scenario
@@ -1664,13 +1765,9 @@ __global__ void k_desired(KArgs a, double* acc) {
   if (sc >= a.B) return;
   const double* st = a.state + (size_t)sc * a.S;
   double* o = acc + (size_t)sc * 6;
-  int f = (a.nforest > 0) ? (a.scen_forest ? a.scen_forest[sc] : 0) : -1;
-  if (f < 0 || a.mountain == nullptr) {
-    double m0[DAT_MOUNTAIN_SIZE] = {30.0, 0.0, 25.0, 1e300, 0.0};
-    desired_accel_forest(st, a.n, m0, 1.5, o);
-  } else {
-    desired_accel_forest(st, a.n, a.mountain + (size_t)f * DAT_MOUNTAIN_SIZE, 1.5, o);
-  }
+  double m[DAT_MOUNTAIN_SIZE];
+  mountain_of(a, sc, m);
+  desired_accel_forest(st, a.n, m, REF_X_OFFSET, o);
 }
 
 __global__ void k_warm(KArgs a) {
@@ -1846,7 +1943,25 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
 // handle + C-ABI
 // ================================================================================================
 constexpr int DAT_MAX_SUB = 4;  // sub-batches of the C-ADMM closed loop (dat_set_sub_batches)
+// The closed loop's log (dat_log_begin .. dat_log_end): device buffers filled by k_rollout_agents<true>, the log
+// clock and what dat_log_clear has dropped.  Held records: HL clock / hl_every - hl_base, step
+// ceil(clock / log_every) - step_base.
+struct dat_log {
+  bool open = false;
+  int nslot = 0, log_every = 1, hl_cap = 0;
+  long long step_cap = 0;
+  int* slot = nullptr;
+  double *hl = nullptr, *step = nullptr;
+  int* sum_iters = nullptr;
+  double* sum_mind = nullptr;
+  unsigned char* sum_col = nullptr;
+  long long clock = 0, hl_base = 0, step_base = 0;
+  std::vector<double> hl_ms;  // per held HL record: device time of the step's control kernels (NaN: sub-batches)
+  long long hl_count(int hl_every) const { return clock / hl_every - hl_base; }
+  long long step_count() const { return (clock + log_every - 1) / log_every - step_base; }
+};
 struct dat_handle {
+  dat_log log;
   dat_config cfg;
   int P = 0, S = 0;
   hipStream_t stream = nullptr;
@@ -2131,17 +2246,62 @@ KArgs sub_kargs(dat_handle* h, int off, int Bs, int s) {
   return a;
 }
 
-int finish_hl(dat_handle* h, int ksteps = 1) {
+// step_ms (optional): the device time of this step's control kernels
+int finish_hl(dat_handle* h, int ksteps = 1, double* step_ms = nullptr) {
   HIPCHK(hipEventSynchronize(h->e1));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
   h->hl_ms += ms;
+  if (step_ms) *step_ms = ms;
   if (h->cfg.mode != DAT_MODE_CENTRALIZED) {  // k_cadmm / k_dd: from after k_bucket to the end of the step
     float mk = 0.f;
     HIPCHK(hipEventElapsedTime(&mk, h->ek, h->e1));
     h->cadmm_ms += mk;
   }
   h->hl_steps += ksteps;
+  return 0;
+}
+
+// the open log's kernel arguments for the sub-batch of scenarios [off, ...) at the current clock
+LogArgs log_args(const dat_handle* h, int off = 0) {
+  const dat_log& g = h->log;
+  LogArgs l;
+  l.slot = g.slot + off;
+  l.hl = g.hl;
+  l.step = g.step;
+  l.sum_iters = offp(g.sum_iters, (size_t)off);
+  l.sum_mind = offp(g.sum_mind, (size_t)off);
+  l.sum_col = offp(g.sum_col, (size_t)off);
+  l.nslot = g.nslot;
+  l.batch = h->cfg.batch;
+  l.hl_every = h->cfg.hl_every;
+  l.log_every = g.log_every;
+  l.clock = g.clock;
+  l.hl_base = g.hl_base;
+  l.step_base = g.step_base;
+  return l;
+}
+
+void log_free(dat_handle* h) {
+  dat_log& g = h->log;
+  (void)hipFree(g.slot);
+  (void)hipFree(g.hl);
+  (void)hipFree(g.step);
+  (void)hipFree(g.sum_iters);
+  (void)hipFree(g.sum_mind);
+  (void)hipFree(g.sum_col);
+  g = dat_log();
+}
+
+// dat_closed_loop with a log open: the call must fit the HL capacity (nothing is dropped silently)
+int log_admit(const dat_handle* h, int hl_steps) {
+  const dat_log& g = h->log;
+  if (!g.open || hl_steps <= 0) return 0;
+  const long long held = g.hl_count(h->cfg.hl_every);
+  if (held + hl_steps > g.hl_cap)
+    return fail("dat_closed_loop: " + std::to_string(hl_steps) + " HL steps on top of the " + std::to_string(held) +
+                " held would pass the log's hl_capacity = " + std::to_string(g.hl_cap) +
+                " (read the log and dat_log_clear, or open it larger); nothing was run");
   return 0;
 }
 
@@ -2318,6 +2478,7 @@ int dat_destroy(dat_handle* h) {
   for (void* p : h->allocs)
     if (p) (void)hipFree(p);
   if (h->acc_seq) (void)hipFree(h->acc_seq);
+  log_free(h);
   for (int s = 1; s < DAT_MAX_SUB; ++s) {
     if (h->sub_stream[s]) (void)hipStreamDestroy(h->sub_stream[s]);
     if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
@@ -2563,8 +2724,17 @@ int closed_loop_sub(dat_handle* h, int hl_steps) {
       HIPCHK(hipEventRecord(ev[0], st));
       if (launch_cadmm(h, a, std::min((Bs + a.G - 1) / a.G, h->persistent_blocks), st)) return -1;
       HIPCHK(hipEventRecord(ev[1], st));
-      launch_rollout(a, Bs, st, h->cfg.hl_every, h->cfg.dt, (const double*)a.fdes);
+      if (h->log.open) {  // the streams run unsynchronised: the record index is this sub-batch's own step count
+        const LogArgs lg = log_args(h, off);
+        launch_rollout(a, Bs, st, h->cfg.hl_every, h->cfg.dt, (const double*)a.fdes, &lg);
+      } else {
+        launch_rollout(a, Bs, st, h->cfg.hl_every, h->cfg.dt, (const double*)a.fdes);
+      }
       HIPCHK(hipGetLastError());
+    }
+    if (h->log.open) {
+      h->log.clock += h->cfg.hl_every;
+      h->log.hl_ms.push_back(std::nan(""));  // no per-step time is defined on overlapping streams
     }
   }
   for (int s = 1; s < S; ++s) {
@@ -2590,6 +2760,7 @@ int closed_loop_sub(dat_handle* h, int hl_steps) {
 
 int dat_closed_loop(dat_handle* h, int hl_steps) {
   if (!h) return fail("null handle");
+  if (log_admit(h, hl_steps)) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->nsub > 1) {
     if (closed_loop_sub(h, hl_steps)) return -1;
@@ -2606,10 +2777,20 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
   for (int s = 0; s < hl_steps; ++s) {
     hipLaunchKernelGGL(k_desired, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
     if (launch_hl(h)) return -1;
-    launch_rollout(a, (int)B, h->stream, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes);
+    if (h->log.open) {
+      const LogArgs lg = log_args(h);
+      launch_rollout(a, (int)B, h->stream, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes, &lg);
+    } else {
+      launch_rollout(a, (int)B, h->stream, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes);
+    }
     HIPCHK(hipGetLastError());
     // waits for this step's control kernel; the rollout still runs while the next step is enqueued
-    if (finish_hl(h)) return -1;
+    double step_ms = 0.0;
+    if (finish_hl(h, 1, &step_ms)) return -1;
+    if (h->log.open) {
+      h->log.clock += h->cfg.hl_every;
+      h->log.hl_ms.push_back(step_ms);
+    }
     h->marks.push_back(now_ms());
   }
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -2984,6 +3165,161 @@ int dat_rp_rollout(dat_handle* h, int steps, const double* f) {
                      (const double*)h->fdes);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- the closed loop's log --------------------------------------------------------------------------------
+int dat_log_begin(dat_handle* h, const int* scenarios, int count, int log_every, int hl_capacity, int summary) {
+  if (!h) return fail("null handle");
+  if (h->log.open) return fail("dat_log_begin: a log is already open (dat_log_end first)");
+  const int B = h->cfg.batch, n = h->cfg.n;
+  if (count < 0 || count > B) return fail("dat_log_begin: count must be in [0, batch]");
+  if (!scenarios && count != 0 && count != B)
+    return fail("dat_log_begin: scenarios = NULL needs count = 0 (none) or count = batch (all)");
+  if (log_every < 1) return fail("dat_log_begin: log_every must be >= 1");
+  if (hl_capacity < 1) return fail("dat_log_begin: hl_capacity must be >= 1");
+  std::vector<int> map((size_t)B, -1);
+  for (int k = 0; k < count; ++k) {
+    const int sc = scenarios ? scenarios[k] : k;
+    if (sc < 0 || sc >= B || (k > 0 && scenarios && sc <= scenarios[k - 1]))
+      return fail("dat_log_begin: scenarios must be strictly increasing indices in [0, batch)");
+    map[sc] = k;
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dat_log& g = h->log;
+  g.nslot = count;
+  g.log_every = log_every;
+  g.hl_cap = hl_capacity;
+  // the logged steps of hl_capacity HL periods, whatever the clock's phase against log_every
+  g.step_cap = ((long long)hl_capacity * h->cfg.hl_every + log_every - 1) / log_every + 1;
+  const size_t rows = (size_t)hl_capacity * B;
+  hipError_t e = hipMalloc((void**)&g.slot, sizeof(int) * (size_t)B);
+  if (e == hipSuccess && count > 0)
+    e = hipMalloc((void**)&g.hl, sizeof(double) * (size_t)hl_capacity * count * DAT_LOG_HL_WORDS(n));
+  if (e == hipSuccess && count > 0)
+    e = hipMalloc((void**)&g.step, sizeof(double) * (size_t)g.step_cap * count * DAT_LOG_ST_WORDS(n));
+  if (e == hipSuccess && summary) e = hipMalloc((void**)&g.sum_iters, sizeof(int) * rows);
+  if (e == hipSuccess && summary) e = hipMalloc((void**)&g.sum_mind, sizeof(double) * rows);
+  if (e == hipSuccess && summary) e = hipMalloc((void**)&g.sum_col, rows);
+  if (e == hipSuccess) e = hipMemcpyAsync(g.slot, map.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    log_free(h);
+    return fail(std::string("dat_log_begin: ") + hipGetErrorString(e));
+  }
+  g.open = true;
+  return 0;
+}
+
+int dat_log_counts(dat_handle* h, long long* hl_records, long long* step_records, long long* clock) {
+  if (!h) return fail("null handle");
+  if (!h->log.open) return fail("dat_log_counts: no log open");
+  if (hl_records) *hl_records = h->log.hl_count(h->cfg.hl_every);
+  if (step_records) *step_records = h->log.step_count();
+  if (clock) *clock = h->log.clock;
+  return 0;
+}
+
+namespace {
+// records [first, first + count) of a full-tier buffer, copied to the host
+int log_fetch(dat_handle* h, const char* who, const double* buf, long long held, int first, int count, size_t words,
+              std::vector<double>* out) {
+  if (!h) return fail("null handle");
+  if (!h->log.open) return fail(std::string(who) + ": no log open");
+  if (first < 0 || count < 0 || (long long)first + count > held)
+    return fail(std::string(who) + ": records [first, first + count) must lie in the " + std::to_string(held) + " held");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t rec = (size_t)h->log.nslot * words;
+  out->resize((size_t)count * rec);
+  if (out->empty()) return 0;
+  HIPCHK(hipMemcpyAsync(out->data(), buf + (size_t)first * rec, sizeof(double) * out->size(), hipMemcpyDeviceToHost,
+                        h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+}  // namespace
+
+int dat_log_read_hl(dat_handle* h, int first, int count, double* f_des, int* iters, int* qp_status, double* min_env_dist,
+                    unsigned char* collision, double* x_ref, double* v_ref, double* solve_ms) {
+  std::vector<double> w;
+  if (log_fetch(h, "dat_log_read_hl", h ? h->log.hl : nullptr, h && h->log.open ? h->log.hl_count(h->cfg.hl_every) : 0,
+                first, count, DAT_LOG_HL_WORDS(h ? h->cfg.n : 3), &w))
+    return -1;
+  const size_t n = h->cfg.n, R = h->log.nslot, HW = DAT_LOG_HL_WORDS(n);
+  for (size_t k = 0; k < (size_t)count * R; ++k) {
+    const double* r = w.data() + k * HW;
+    int ri[2 + NMAX];
+    memcpy(ri, r + DAT_LOG_HL_INTS(n), sizeof(int) * (2 + n));
+    if (f_des) memcpy(f_des + k * 3 * n, r, sizeof(double) * 3 * n);
+    if (iters) iters[k] = ri[0];
+    if (collision) collision[k] = (unsigned char)ri[1];
+    if (qp_status) memcpy(qp_status + k * n, ri + 2, sizeof(int) * n);
+    if (min_env_dist) min_env_dist[k] = r[DAT_LOG_HL_MIND(n)];
+    if (x_ref) memcpy(x_ref + 3 * k, r + DAT_LOG_HL_XREF(n), sizeof(double) * 3);
+    if (v_ref) memcpy(v_ref + 3 * k, r + DAT_LOG_HL_VREF(n), sizeof(double) * 3);
+  }
+  if (solve_ms)
+    for (int k = 0; k < count; ++k) solve_ms[k] = h->log.hl_ms[(size_t)first + k];
+  return 0;
+}
+
+int dat_log_read_steps(dat_handle* h, int first, int count, long long* step_index, double* thrust, double* moment,
+                       double* state, double* x_err, double* v_err) {
+  std::vector<double> w;
+  if (log_fetch(h, "dat_log_read_steps", h ? h->log.step : nullptr, h && h->log.open ? h->log.step_count() : 0, first,
+                count, DAT_LOG_ST_WORDS(h ? h->cfg.n : 3), &w))
+    return -1;
+  const size_t n = h->cfg.n, R = h->log.nslot, SW = DAT_LOG_ST_WORDS(n), S = DAT_STATE_SIZE(n);
+  for (size_t k = 0; k < (size_t)count * R; ++k) {
+    const double* r = w.data() + k * SW;
+    for (size_t i = 0; i < n; ++i) {
+      if (thrust) thrust[k * n + i] = r[4 * i];
+      if (moment) memcpy(moment + (k * n + i) * 3, r + 4 * i + 1, sizeof(double) * 3);
+    }
+    if (state) memcpy(state + k * S, r + DAT_LOG_ST_STATE(n), sizeof(double) * S);
+    if (x_err) x_err[k] = r[DAT_LOG_ST_XERR(n)];
+    if (v_err) v_err[k] = r[DAT_LOG_ST_XERR(n) + 1];
+  }
+  if (step_index)
+    for (int k = 0; k < count; ++k) step_index[k] = (h->log.step_base + first + k) * h->log.log_every;
+  return 0;
+}
+
+int dat_log_read_summary(dat_handle* h, int first, int count, int* iters, double* min_env_dist,
+                         unsigned char* collision) {
+  if (!h) return fail("null handle");
+  const dat_log& g = h->log;
+  if (!g.open || !g.sum_iters) return fail("dat_log_read_summary: no log with the summary tier open");
+  const long long held = g.hl_count(h->cfg.hl_every);
+  if (first < 0 || count < 0 || (long long)first + count > held)
+    return fail("dat_log_read_summary: records [first, first + count) must lie in the " + std::to_string(held) + " held");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t B = h->cfg.batch, o = (size_t)first * B, m = (size_t)count * B;
+  if (m == 0) return 0;
+  if (iters) HIPCHK(hipMemcpyAsync(iters, g.sum_iters + o, sizeof(int) * m, hipMemcpyDeviceToHost, h->stream));
+  if (min_env_dist)
+    HIPCHK(hipMemcpyAsync(min_env_dist, g.sum_mind + o, sizeof(double) * m, hipMemcpyDeviceToHost, h->stream));
+  if (collision) HIPCHK(hipMemcpyAsync(collision, g.sum_col + o, m, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dat_log_clear(dat_handle* h) {
+  if (!h) return fail("null handle");
+  dat_log& g = h->log;
+  if (!g.open) return fail("dat_log_clear: no log open");
+  g.hl_base = g.clock / h->cfg.hl_every;
+  g.step_base = (g.clock + g.log_every - 1) / g.log_every;
+  g.hl_ms.clear();
+  return 0;
+}
+
+int dat_log_end(dat_handle* h) {
+  if (!h) return fail("null handle");
+  if (!h->log.open) return fail("dat_log_end: no log open");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  log_free(h);
   return 0;
 }
 

@@ -814,16 +814,23 @@ DAT_HD void rp_step(const double* prm, int n, double* st, int* counter, const do
   }
 }
 
-// _desired_acceleration_forest (example/rqp_example.py:33-59); acc = (dvl_des, dwl_des)
-DAT_HD void desired_accel_forest(const double* st, int n, const double* mountain, double x_offset, double* acc) {
-  const double* xl = st + DAT_S_XL(n);
-  const double* vl = st + DAT_S_VL(n);
-  double xr[3] = {xl[0] + x_offset, 0.0, 1.5};
+// x_ref, v_ref of _desired_acceleration_forest (example/rqp_example.py:36-48) at the payload position xl: the
+// references the desired-acceleration law tracks and the closed loop's recorder logs the errors against
+DAT_HD void forest_references(const double* xl, const double* mountain, double x_offset, double* xr, double* vr) {
+  xr[0] = xl[0] + x_offset; xr[1] = 0.0; xr[2] = 1.5;
   double dx = xl[0] - mountain[DAT_M_CX], dy = xl[1] - mountain[DAT_M_CY];
   double nn = sqrt(dx * dx + dy * dy);
   if (nn < mountain[DAT_M_RADIUS])
     xr[2] = sqrt(mountain[DAT_M_SPHERE_R] * mountain[DAT_M_SPHERE_R] - nn * nn) - mountain[DAT_M_DEPTH] + 1.5;
-  double vr[3] = {0.5, 0.0, 0.0};
+  vr[0] = 0.5; vr[1] = 0.0; vr[2] = 0.0;
+}
+
+// _desired_acceleration_forest (example/rqp_example.py:33-59); acc = (dvl_des, dwl_des)
+DAT_HD void desired_accel_forest(const double* st, int n, const double* mountain, double x_offset, double* acc) {
+  const double* xl = st + DAT_S_XL(n);
+  const double* vl = st + DAT_S_VL(n);
+  double xr[3], vr[3];
+  forest_references(xl, mountain, x_offset, xr, vr);
   double d[3];
   for (int c = 0; c < 3; ++c) d[c] = -(vl[c] - vr[c]) - (xl[c] - xr[c]);
   double dn = sqrt(dot3(d, d));

@@ -121,6 +121,25 @@ struct KArgs {
   int tmode;                     // k_cadmm_tail: 0 the hand-over lists (rlist), 1 the tail-routed stretch of slist
 };
 
+// The closed loop's recorder (dat_log_*), handed to k_rollout_agents<true> at every HL step: where the records
+// go and the log clock at the launch.  Record layouts: dat_layout.h (DAT_LOG_*).  A launch writes the HL record
+// clock / hl_every - hl_base and the step records ceil(i / log_every) - step_base of its logged steps
+// i = clock + s, i % log_every == 0: indices fixed by the clock, so no atomics.
+struct LogArgs {
+  const int* slot;         // [B] scenario -> slot of the full tier, -1: not recorded (offset per sub-batch)
+  double* hl;              // full tier, HL records
+  double* step;            // full tier, step records
+  int* sum_iters;          // summary tier [record][batch] (offset per sub-batch); null: off
+  double* sum_mind;
+  unsigned char* sum_col;
+  int nslot;               // recorded scenarios
+  int batch;               // scenarios of the handle (the summary tier's row length)
+  int hl_every, log_every;
+  long long clock;         // simulation steps run by dat_closed_loop since dat_log_begin, at this launch
+  long long hl_base, step_base;  // records dropped by dat_log_clear
+};
+struct NoLog {};
+
 // wave-uniform maximum (every lane of the wavefront must execute it)
 __device__ inline int wave_max(int v) {
   for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));

@@ -58,6 +58,21 @@
 #define DAT_M_DEPTH 4
 #define DAT_MOUNTAIN_SIZE 5
 
+// ---- records of the closed loop's log (dat_log_*), in 8-byte words, laid out [record][slot][word] --------
+// HL record (after control step k): f_des (3n, agent-major), min_env_dist, x_ref (3), v_ref (3), then 32-bit
+// ints packed two per word: iters, collision, qp_status (n), padded to a whole word.
+#define DAT_LOG_HL_MIND(n) (3 * (n))
+#define DAT_LOG_HL_XREF(n) (3 * (n) + 1)
+#define DAT_LOG_HL_VREF(n) (3 * (n) + 4)
+#define DAT_LOG_HL_INTS(n) (3 * (n) + 7)  // int[0] iters, int[1] collision, int[2 + i] qp_status of agent i
+#define DAT_LOG_HL_WORDS(n) (3 * (n) + 7 + ((n) + 3) / 2)
+// step record (simulation step i): per agent (thrust, moment (3)) applied at step i (4n), the state after the
+// step in the state layout (DAT_STATE_SIZE(n)), x_err, v_err.  A multiple of 4 words: every record and every
+// agent's (thrust, moment) start on a 32-byte boundary.
+#define DAT_LOG_ST_STATE(n) (4 * (n))
+#define DAT_LOG_ST_XERR(n) (4 * (n) + DAT_STATE_SIZE(n))
+#define DAT_LOG_ST_WORDS(n) (4 * (n) + DAT_STATE_SIZE(n) + 2)
+
 #define DAT_BARK_RADIUS 0.3
 #define DAT_BARK_HALF_HEIGHT 2.0
 #define DAT_NENV 10            // env CBF rows per QP (control/rqp_cadmm.py:218)

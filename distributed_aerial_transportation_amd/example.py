@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import scenarios
+from . import layout, scenarios
 from .env_forest import Forest
 from .system import RQPState, pack_state
 
@@ -78,12 +78,82 @@ def references(xl: np.ndarray, forest) -> tuple:
     return x_ref, v_ref
 
 
+LOG_ARRAYS_HL = ("f_des", "iters", "min_env_dist", "solve_ms")
+LOG_ARRAYS_STEP = ("thrust", "moment", "state", "x_err", "v_err")
+
+
+def logs_from_arrays(headers: List[dict], arrays: dict, n: int) -> List[dict]:
+    """The reference's logs dicts (example/rqp_example.py:141-160) from the time-major arrays of
+    ``BatchedController.log_read`` (several reads concatenated along axis 0): headers[r] holds the run's
+    constants of recorded scenario r (n, dt, T, ..., controller_type), arrays the keys LOG_ARRAYS_HL
+    ((K, R, ...), solve_ms (K,)) and LOG_ARRAYS_STEP ((Ks, R, ...)).  Pure: every field is sliced out of the
+    whole arrays at once; only the per-record objects the format asks for (a list entry, an RQPStateData) are
+    made one by one."""
+    st = np.asarray(arrays["state"])
+    Ks, R = st.shape[:2]
+    o = {k: layout.s_off(k, n) for k in ("R", "W", "XL", "VL", "RL", "WL")}
+    Rq = st[..., o["R"]:o["R"] + 9 * n].reshape(Ks, R, n, 3, 3).transpose(1, 0, 3, 4, 2).copy()
+    wq = st[..., o["W"]:o["W"] + 3 * n].reshape(Ks, R, n, 3).transpose(1, 0, 3, 2).copy()
+    xl = st[..., o["XL"]:o["XL"] + 3].transpose(1, 0, 2).copy()
+    vl = st[..., o["VL"]:o["VL"] + 3].transpose(1, 0, 2).copy()
+    Rl = st[..., o["RL"]:o["RL"] + 9].reshape(Ks, R, 3, 3).transpose(1, 0, 2, 3).copy()
+    wl = st[..., o["WL"]:o["WL"] + 3].transpose(1, 0, 2).copy()
+    # scenario-major copies: logs[r]'s entries are views of row r
+    f_des = np.swapaxes(np.asarray(arrays["f_des"]), 0, 1).copy()
+    thrust = np.swapaxes(np.asarray(arrays["thrust"]), 0, 1).copy()
+    moment = np.swapaxes(np.asarray(arrays["moment"]), 0, 1).copy()
+    iters = np.asarray(arrays["iters"]).T
+    min_env_dist = np.asarray(arrays["min_env_dist"], float).T.tolist()
+    x_err = np.asarray(arrays["x_err"], float).T.tolist()
+    v_err = np.asarray(arrays["v_err"], float).T.tolist()
+    solve_time = (np.asarray(arrays["solve_ms"], float) * 1e-3).tolist()
+    logs = []
+    for r in range(R):
+        lg = dict(headers[r])
+        lg["state_seq"] = [RQPStateData(*s) for s in zip(Rq[r], wq[r], xl[r], vl[r], Rl[r], wl[r])]
+        lg["x_err_seq"] = x_err[r]
+        lg["v_err_seq"] = v_err[r]
+        lg["f_des_seq"] = list(f_des[r])
+        lg["iter_seq"] = iters[r][iters[r] != -1].tolist()  # centralized: no iteration count (:126-127)
+        lg["solve_time_seq"] = list(solve_time)
+        lg["min_env_dist_seq"] = min_env_dist[r]
+        lg["w_seq"] = list(zip(thrust[r], moment[r]))
+        logs.append(lg)
+    return logs
+
+
+def _simulate_resident(eng, headers: List[dict], n: int, hl_steps: int, log_freq: int, record, chunk_hl: int,
+                       hl_rel_freq: int, dt: float, progress: bool) -> List[dict]:
+    """The loop on dat_closed_loop, recorded on the device: chunks of chunk_hl HL steps, each read out and cleared."""
+    chunk_hl = max(1, min(int(chunk_hl), hl_steps))
+    eng.log_begin(record, log_every=log_freq, hl_capacity=chunk_hl)
+    parts = []
+    done = 0
+    while done < hl_steps or not parts:
+        k = min(chunk_hl, hl_steps - done)
+        eng.closed_loop(k)
+        parts.append(eng.log_read())
+        eng.log_clear()
+        done += k
+        if progress:
+            print(f"t = {done * hl_rel_freq * dt:.2f} s", flush=True)
+    eng.log_end()
+    arrays = {k: np.concatenate([p[k] for p in parts]) for k in LOG_ARRAYS_HL + LOG_ARRAYS_STEP}
+    return logs_from_arrays([headers[b] for b in parts[0]["scenarios"]], arrays, n)
+
+
 def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scenario_forest=None, n: int = 3,
                    T: float = 100.0, dt: float = 1e-3, hl_rel_freq: int = 10, log_freq: Optional[int] = None,
                    so3_controller_type: str = "pd", params: Optional[np.ndarray] = None, device: int = 0,
-                   progress: bool = False) -> List[dict]:
+                   progress: bool = False, resident: bool = False, record=None, chunk_hl: int = 100) -> List[dict]:
     """B closed loops of example/rqp_example.py:main on one GPU; states (B, 12n + 18) (packed
-    RQPState), forests[scenario_forest[b]] the forest of scenario b.  Returns one logs dict per scenario."""
+    RQPState), forests[scenario_forest[b]] the forest of scenario b.  Returns one logs dict per scenario.
+
+    resident=True runs the loop on the device-resident closed loop (dat_closed_loop) and has it record the logs
+    in HBM (dat_log_*): nothing is copied per step, the records are read every chunk_hl HL steps.  record: the
+    scenarios whose dicts are returned (strictly increasing indices; default all).  The resident loop runs whole
+    HL periods: a step count that is no multiple of hl_rel_freq raises ValueError.  The default (resident=False)
+    drives the loop from the host step by step and returns every scenario's dict."""
     from .control import BatchedController
 
     if controller_type not in CONTROLLER_TYPES:
@@ -93,11 +163,23 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
     B = states.shape[0]
     sf = np.zeros(B, dtype=np.int32) if scenario_forest is None else np.asarray(scenario_forest, dtype=np.int32)
     prm = scenarios.params_block(n) if params is None else params
+    if resident and len(np.arange(0, T, dt)) % hl_rel_freq != 0:
+        raise ValueError(f"resident=True runs whole HL periods: {len(np.arange(0, T, dt))} steps (T / dt) is no "
+                         f"multiple of hl_rel_freq = {hl_rel_freq}")
     eng = BatchedController(controller_type, n, B, prm, dt=dt, hl_every=hl_rel_freq, device=device)
     eng.set_forests(forests, sf)
     eng.set_low_level(so3_controller_type)
     eng.set_state(states, np.zeros(B, dtype=np.int32))
     steps = len(np.arange(0, T, dt))  # t_seq = np.arange(0, T, dt) (:107)
+    if resident:
+        headers = [dict(n=n, dt=dt, T=T, hl_rel_freq=hl_rel_freq, log_freq=log_freq,
+                        num_trees=forests[sf[b]].num_trees, tree_pos=forests[sf[b]].tree_pos,
+                        controller_type=controller_type) for b in range(B)]
+        try:
+            return _simulate_resident(eng, headers, n, steps // hl_rel_freq, log_freq, record, chunk_hl, hl_rel_freq,
+                                      dt, progress)
+        finally:
+            eng.close()
     logs = [dict(n=n, dt=dt, T=T, hl_rel_freq=hl_rel_freq, log_freq=log_freq,
                  num_trees=forests[sf[b]].num_trees, tree_pos=forests[sf[b]].tree_pos, controller_type=controller_type,
                  state_seq=[], x_err_seq=[], v_err_seq=[], f_des_seq=[], iter_seq=[], solve_time_seq=[],
@@ -145,20 +227,20 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
 
 def simulate(controller_type: str = "dual-decomposition", n: int = 3, T: float = 100.0, dt: float = 1e-3,
              hl_rel_freq: int = 10, log_freq: Optional[int] = None, env=None, state: Optional[RQPState] = None,
-             so3_controller_type: str = "pd", device: int = 0, verbose: bool = True) -> dict:
+             so3_controller_type: str = "pd", device: int = 0, verbose: bool = True, resident: bool = False) -> dict:
     """example/rqp_example.py:main on the GPU for one scenario (rqp_setup(n) start state, Forest()
     environment -- pass env = Forest.seeded(s) for a reproducible layout); prints the statistics of
-    :140 and returns the logs dict of :141-165."""
+    :140 and returns the logs dict of :141-165.  resident: as in simulate_batch."""
     env = Forest() if env is None else env
     if state is None:
         _, _, state = scenarios.rqp_setup(n)
     logs = simulate_batch(controller_type, pack_state(state)[None], [env], None, n=n, T=T, dt=dt,
                           hl_rel_freq=hl_rel_freq, log_freq=log_freq, so3_controller_type=so3_controller_type,
-                          device=device)[0]
+                          device=device, resident=resident)[0]
     if verbose:
         print_stats(logs["iter_seq"], logs["solve_time_seq"])
     return logs
 
 
 __all__ = ["RQPStateData", "simulate", "simulate_batch", "print_stats", "save_logs", "compute_aggregate_statistics",
-           "references"]
+           "references", "logs_from_arrays"]

@@ -157,6 +157,55 @@ int dat_set_sub_batches(dat_handle* h, int count);
  * run are marked (2 marks), so consecutive differences give one whole-run time, not per-step times. */
 int dat_get_step_marks(dat_handle* h, double* marks_ms, int max_marks);
 
+/* ---- the closed loop's log: what the reference's loop keeps in its lists (state_seq, x_err_seq, v_err_seq,
+ * f_des_seq, iter_seq, solve_time_seq, min_env_dist_seq, w_seq: example/rqp_example.py:112-138), recorded in HBM
+ * by the rollout kernel of dat_closed_loop itself and read after the run; nothing is copied per step.
+ *
+ * dat_log_begin opens a log on the handle.  scenarios[count]: the scenarios whose full records are kept, strictly
+ * increasing indices in [0, B) (NULL with count = 0: none; NULL with count = B: all); a recorded scenario's place
+ * in that list is its slot.  log_every >= 1 is the reference's log_freq in simulation steps (it need neither
+ * divide hl_every nor be a multiple of it); hl_capacity >= 1 the number of HL steps the buffers hold; summary != 0
+ * also keeps the summary tier of all B scenarios.  Allocates every buffer and zeroes the log clock.  Errors (a log
+ * already open, bad arguments, an allocation failure) leave no log open.
+ *
+ * The log clock counts the simulation steps run by dat_closed_loop since dat_log_begin; every dat_closed_loop
+ * call starts at an HL instant, so it is a multiple of hl_every between calls.  dat_control_step,
+ * dat_control_steps, dat_rollout and dat_rp_rollout are NOT recorded and do not advance the clock while a log is
+ * open.  A dat_closed_loop call that would pass hl_capacity returns an error before it launches anything:
+ * states, warm state and log are untouched (dat_log_read_*, dat_log_clear, then call again).
+ *
+ * Full tier, per slot:
+ *   HL record k, after control step k (example/rqp_example.py:121-129): f_des (3n, agent-major), iters (-1 for
+ *     centralized), qp_status (n), min_env_dist, collision, and x_ref (3), v_ref (3) of the desired-acceleration
+ *     law at that HL instant (:36-48, :122).
+ *   step record at every clock value i with i % log_every == 0 (:132-138): thrust (n) and moment (n x 3,
+ *     agent-major) the low-level law applied at step i (:130), the state after step i (DAT_STATE_SIZE(n), the
+ *     state layout), x_err = |x_ref - xl| and v_err = |v_ref - vl| against the references of the HL instant
+ *     that opened the current HL period (:134-135).
+ * Summary tier, per HL step and for all B scenarios: iters, min_env_dist, collision (:126-129 and
+ *   stats.collision) -- enough to find which scenarios collide and when without stepping the loop from the host.
+ * Host side, per HL step: the device time [ms] of the step's control kernels (stats.solve_time, :128; the
+ *   per-step share of dat_get_counters' hl_kernel_ms); NaN with sub-batch streams, where steps overlap. */
+int dat_log_begin(dat_handle* h, const int* scenarios, int count, int log_every, int hl_capacity, int summary);
+/* Records held (written since dat_log_begin or the last dat_log_clear) and the log clock; any pointer may be NULL. */
+int dat_log_counts(dat_handle* h, long long* hl_records, long long* step_records, long long* clock);
+/* Copy held records [first, first + count) to the caller, time-major [record][slot][...]; any output pointer may
+ * be NULL.  dat_log_read_hl: f_des count x slots x 3n, iters count x slots, qp_status count x slots x n,
+ * min_env_dist count x slots, collision count x slots, x_ref and v_ref count x slots x 3, solve_ms count.
+ * dat_log_read_steps: step_index count (the clock value i of each record), thrust count x slots x n, moment
+ * count x slots x n x 3, state count x slots x DAT_STATE_SIZE(n), x_err and v_err count x slots.
+ * dat_log_read_summary (needs summary != 0): iters, min_env_dist, collision count x B, per HL record. */
+int dat_log_read_hl(dat_handle* h, int first, int count, double* f_des, int* iters, int* qp_status, double* min_env_dist,
+                    unsigned char* collision, double* x_ref, double* v_ref, double* solve_ms);
+int dat_log_read_steps(dat_handle* h, int first, int count, long long* step_index, double* thrust, double* moment,
+                       double* state, double* x_err, double* v_err);
+int dat_log_read_summary(dat_handle* h, int first, int count, int* iters, double* min_env_dist,
+                         unsigned char* collision);
+/* dat_log_clear empties the buffers and keeps the clock (a long run is read out in chunks of hl_capacity HL
+ * steps); dat_log_end frees the buffers and closes the log (dat_destroy does so for an open log). */
+int dat_log_clear(dat_handle* h);
+int dat_log_end(dat_handle* h);
+
 /* ---- counters since the last reset: agent-QP solves, IPM iterations, IPM iterations x active
  * constraint rows (for the flop model of DESIGN.md 3.1), control steps, and the summed device time
  * of the high-level kernels [ms] (HIP events on the handle stream).  Any pointer may be NULL. */

@@ -2,7 +2,9 @@
 which scenarios collide and at which step, and a fixture of the earliest ones for the oracle replay
 (tests/test_collision_replay.py): each scenario's state `lead` steps before its first collision, and the GPU's own
 replay from there with the warm state reset (the replay's start in the oracle as well) -- per step f_des, ADMM
-iterations, min env distance and the collision flag.
+iterations, min env distance and the collision flag.  The 65,536-scenario loop runs device-resident
+(dat_closed_loop) with the recorder open (dat_log_*): its summary tier gives the collision flags of pass 1, its
+full tier on the picked scenarios their states of pass 2; nothing is stepped from the host.
 
     python tools/collision_replay.py out.npz [--steps 1000] [--count 4] [--lead 3] [--after 2]   # on the GPU box
 """
@@ -18,6 +20,7 @@ sys.path.insert(0, ROOT)
 
 N = 6
 B = 65536
+CHUNK = 100  # HL steps per read of the recorder
 
 
 def engine(forests, sf, states):
@@ -45,20 +48,22 @@ def main():
     import bench
 
     sf, states, forests = bench.bench_states(N, B, 0, 1, 64, "path", None)
-    # pass 1: the loop step by step (control, then the 10 low-level steps: one closed-loop HL step), the
-    # scenarios' collision flags
+    # pass 1: the device-resident loop with the recorder's summary tier (dat_log_*), read out every CHUNK HL
+    # steps: the scenarios' collision flags per step, nothing stepped from the host
     eng = engine(forests, sf, states)
     first = np.full(B, -1)
     hits = np.zeros(B, dtype=np.int64)
     t0 = time.time()
-    for k in range(args.steps):
-        r = eng.control()
-        new = r.collision & (first < 0)
-        first[new] = k
-        hits += r.collision
-        eng.rollout(10)
-        if k % 100 == 0:
-            print(f"step {k}: {int((first >= 0).sum())} scenarios collided so far ({time.time() - t0:.0f} s)", flush=True)
+    eng.log_begin([], hl_capacity=CHUNK, summary=True)
+    for k0 in range(0, args.steps, CHUNK):
+        eng.closed_loop(min(CHUNK, args.steps - k0))
+        col = eng.log_read()["sum_collision"]  # (HL steps of the chunk, B)
+        eng.log_clear()
+        new = col.any(axis=0) & (first < 0)
+        first[new] = k0 + col[:, new].argmax(axis=0)
+        hits += col.sum(axis=0)
+        print(f"step {k0 + len(col)}: {int((first >= 0).sum())} scenarios collided so far ({time.time() - t0:.0f} s)",
+              flush=True)
     eng.close()
     ids = np.flatnonzero(first >= 0)
     print(f"{len(ids)} scenarios collide ({int(hits.sum())} scenario-steps); first collisions at steps "
@@ -68,17 +73,22 @@ def main():
         return
     pick = ids[np.argsort(first[ids], kind="stable")[:args.count]]
     s0 = first[pick] - args.lead
-    # pass 2: the same loop (deterministic) up to each picked scenario's start step, its state there
+    # pass 2: the same loop (deterministic) up to each picked scenario's start step with the full tier open on
+    # the picked scenarios, every simulation step logged: the state at HL instant k is the one after step
+    # 10 k - 1, the polar-projection counter there (10 k) % 20 (it starts at 0 and wraps at 20)
+    order = np.argsort(pick)
     eng = engine(forests, sf, states)
     st0 = np.zeros((len(pick), states.shape[1]))
-    c0 = np.zeros(len(pick), dtype=np.int32)
-    for k in range(int(s0.max()) + 1):
-        at = np.flatnonzero(s0 == k)
-        if len(at):
-            st, c = eng.get_state()
-            st0[at], c0[at] = st[pick[at]], c[pick[at]]
-        r = eng.control()
-        eng.rollout(10)
+    st0[s0 <= 0] = states[pick[s0 <= 0]]
+    c0 = ((10 * np.maximum(s0, 0)) % 20).astype(np.int32)
+    eng.log_begin(pick[order], log_every=1, hl_capacity=CHUNK)
+    for k0 in range(0, int(s0.max()), CHUNK):
+        eng.closed_loop(min(CHUNK, int(s0.max()) - k0))
+        out = eng.log_read()
+        eng.log_clear()
+        for q in np.flatnonzero((s0 > k0) & (s0 <= k0 + len(out["f_des"]))):
+            at = int(np.flatnonzero(out["step_index"] == 10 * s0[q] - 1)[0])
+            st0[q] = out["state"][at, int(np.flatnonzero(order == q)[0])]
     eng.close()
     # the GPU replay from st0 with the warm state reset
     K = args.lead + 1 + args.after
