@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import Any, List, Optional
+from typing import Any, List, Optional, Tuple
 
 import numpy as np
 
@@ -211,6 +211,26 @@ class BatchedController:
     def set_sub_batches(self, count: int) -> None:
         """dat_set_sub_batches: closed_loop on `count` sub-batches with one stream each (C-ADMM)."""
         L.check(self._lib.dat_set_sub_batches(self._h, int(count)))
+
+    def set_advance_overlap(self, on: bool) -> None:
+        """dat_set_advance_overlap: the closed loop's early advance of finished scenarios beside the drain."""
+        L.check(self._lib.dat_set_advance_overlap(self._h, int(bool(on))))
+
+    def advance_counts(self) -> Tuple[int, int]:
+        """Scenario-steps advanced by the (early, late) pass of the advance overlap since the last reset."""
+        e, l = ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(self._lib.dat_get_advance_counts(self._h, ctypes.byref(e), ctypes.byref(l)))
+        return e.value, l.value
+
+    def debug_advance_split(self, early_mask) -> None:
+        """dat_debug_advance_split (tests): a fixed early / late split by mask; None clears it."""
+        if early_mask is None:
+            L.check(self._lib.dat_debug_advance_split(self._h, None))
+            return
+        m = np.ascontiguousarray(np.asarray(early_mask) != 0, dtype=np.uint8)
+        if m.shape != (self.batch,):
+            raise ValueError("early_mask must have one entry per scenario")
+        L.check(self._lib.dat_debug_advance_split(self._h, L.ptr(m, L.U8)))
 
     def closed_loop(self, hl_steps: int) -> None:
         L.check(self._lib.dat_closed_loop(self._h, int(hl_steps)))

@@ -391,6 +391,9 @@ __device__ EnvOut env_rows_coop(const double* prm, int n, const double* st, cons
 // the bound (290 registers, no scratch, one wavefront per SIMD) measured slower, C4 A/B 3.58 / 3.61 ->
 // 3.70 / 3.80 ms per step (round 4).  Three or four wavefronts per SIMD (168 / 128 VGPRs, the sorted row
 // slots spilled) measured 3.2-3.6x slower by kernel trace: 0.24 -> 0.77 / 0.87 ms (round 4).
+// ADV (dat_kargs.hpp): the scenarios that take part; a scenario's lanes do together or not at all, the others are
+// carried through the barriers like the lanes past the batch.  ADV_ALL compiles to the kernel without a gate.
+template <int ADV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_env_class(KArgs a) {
   __shared__ int nd[64], cl[64];
   __shared__ double md[64];
@@ -399,7 +402,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
   const int lane = threadIdx.x;
   const int ls = lane / n, i = lane - ls * n;
   const int sc = blockIdx.x * G + ls;
-  const bool valid = (lane < NT) && (sc < a.B);
+  const bool valid = (lane < NT) && (sc < a.B) && adv_gate<ADV, false>(a, sc);
+  if constexpr (ADV != ADV_ALL)
+    if (!__syncthreads_or(valid)) return;  // no scenario of the block takes part
   int need = 0, col = 0;
   double dist = 1e300;
   const double* prm = valid ? prm_of(a, sc) : a.params;
@@ -443,11 +448,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
     // previous step's ADMM iterations, then its slowest agent QP's IPM iterations: within a class the
     // longest scenarios are claimed first and scenarios sharing a wavefront tend to need similar
     // numbers of ADMM passes and of IPM iterations per pass (a pass lasts as long as its slowest lane)
-    const int bin = NPB * iter_bin(a.iters[sc]) + ipm_bin(a.ipmx[sc]);
+    // (beside the running drain the two come as the drain published them: write-through, read past the caches)
+    const int pit = ADV == ADV_EARLY ? ld_wt(a.iters + sc) : a.iters[sc];
+    const int pmx = ADV == ADV_EARLY ? ld_wt(a.ipmx + sc) : a.ipmx[sc];
+    const int bin = NPB * iter_bin(pit) + ipm_bin(pmx);
     // a scenario wedged in a stall (previous step > TAIL_PREV passes) goes to the tail (key NKEY + class); with
     // sub-batches it stays in k_cadmm's queue, which hands it over after its first pass (the tail rule), the
     // same arithmetic
-    a.need[sc] = a.route && tail_wedged(a.iters[sc], a.tail_prev) ? NKEY + cls : cls * NIB + (NIB - 1 - bin);
+    a.need[sc] = a.route && tail_wedged(pit, a.tail_prev) ? NKEY + cls : cls * NIB + (NIB - 1 - bin);
     a.col[sc] = (unsigned char)c;
     a.mind[sc] = m;
     cnum = c;
@@ -565,7 +573,11 @@ __device__ __forceinline__ void flush_solve_counters(const KArgs& a, unsigned lo
 // the previous pass and the stall exit (ipm_solve WS).  Built with -ffp-contract=on (multiply-adds fused within
 // an expression only), the inlined fast solver computes the same bits in either kernel, and the tail rule
 // depends on the scenario's own history: a scenario's results do not depend on which kernel ran which pass.
-template <int CLS, bool RB>
+// ADV: the drain of the closed loop's advance overlap (closed_loop_overlap): a stopped scenario's f_des, iters and
+// ipmx are stored write-through and stamped in KArgs::done, and k_cadmm's class-0 drain tells the host when its
+// queue has been claimed empty.  Without it k_cadmm / k_cadmm0 are compiled without any of that; the tail kernels
+// exist once and go by KArgs::done at run time (a second instantiation changes how their solver is inlined).
+template <int CLS, bool RB, bool ADV>
 __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
   constexpr bool ENV = CLS > 0;
   constexpr int NR = cadmm_nr(CLS);
@@ -585,7 +597,13 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
   const bool TM = RB && a.tmode == 1;  // the tail-routed stretch of slist (k_env_class), not the hand-over list
   const int first = a.scount[sc_at(TM ? SC_TAIL_START : SC_START, CLS)];
   const int cnt = a.scount[sc_at(TM ? SC_TAIL_SIZE : RB ? SC_HAND_SIZE : SC_SIZE, CLS)];
-  if (cnt == 0) return;
+  if (cnt == 0) {
+    // (an empty class 0 is claimed empty from the start: the advance overlap's signal, see the refill)
+    if constexpr (ADV && !RB && CLS == 0)
+      if (blockIdx.x == 0 && lane == 0)
+        __hip_atomic_store(a.qempty, a.serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return;
+  }
   int* const qh = a.scount + sc_at(TM ? SC_TAIL_HEAD : RB ? SC_HAND_HEAD : SC_HEAD, CLS);
   const int* const ql = (RB && !TM ? a.rlist : a.slist) + first;
   const int rmode = RB ? 3 : cadmm_row_mode(n, G, CLS);  // wave-uniform
@@ -621,6 +639,10 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     if (lane < NT && i == 0 && vi == 0 && L.sid[ls] == -1) {
       const int q = atomicAdd(qh, 1);
       const int s2 = q < cnt ? ql[q] : -2;  // -2: queue drained, slot retires
+      // the advance overlap: the first claim past the end of k_cadmm's last queue tells the host that most of the
+      // batch is finished and the launch is ramping down (one system-scope store to mapped host memory)
+      if constexpr (ADV && !RB && CLS == 0)
+        if (q == cnt) __hip_atomic_store(a.qempty, a.serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       L.sid[ls] = s2;
       L.done[ls] = 0;
       L.wmx[ls] = RB && !TM && s2 >= 0 ? a.rres[(size_t)s2 * RRES_INTS + RRES_WMX] : 0;
@@ -841,16 +863,33 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
           atomicAdd(a.counters + CNT_ROB, 1ull);
           if (TM && kstep == 0) atomicAdd(a.counters + CNT_TAIL + 2, 1ull);
         }
+        // (ADV: what the early rollout and env rows of the scenario read while this kernel still runs -- f_des,
+        // iters, ipmx -- goes out write-through; the closed loop does not fuse steps, so this is the scenario's
+        // last one)
+        const bool wt = RB ? a.done != nullptr : ADV;  // (k_cadmm: fixed at compile time; the tail: per launch)
         if (vi == 0) {
           for (int c = 0; c < 3; ++c) {
             a.cfbar[(size_t)sc * N3 + 3 * i + c] = fb[3 * i + c];
-            a.fdes[(size_t)sc * N3 + 3 * i + c] = myf[3 * i + c];  // f_app = diag copies (:669-671)
+            // f_app = diag copies (:669-671)
+            if (wt) st_wt(a.fdes + (size_t)sc * N3 + 3 * i + c, myf[3 * i + c]);
+            else a.fdes[(size_t)sc * N3 + 3 * i + c] = myf[3 * i + c];
           }
           a.qstatus[(size_t)sc * n + i] = qstat;
           if (i == 0) {
-            a.iters[sc] = iter;
-            a.ipmx[sc] = L.wmx[ls];
+            if (wt) {
+              st_wt(a.iters + sc, iter);
+              st_wt(a.ipmx + sc, L.wmx[ls]);
+            } else {
+              a.iters[sc] = iter;
+              a.ipmx[sc] = L.wmx[ls];
+            }
           }
+        }
+        if (wt) {
+          // the stamp follows the wavefront's stores (all the scenario's lanes are in this wavefront).  No fence:
+          // the bytes above left the L2 with their stores
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          if (i == 0 && vi == 0) st_wt(a.done + sc, a.serial);
         }
         if (kstep + 1 < a.ksteps) {
           // fused steps: the scenario's next control step in the same slot (warm f, f_mean, lambda kept;
@@ -899,11 +938,12 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
 // instantiation of the IPM.  All wavefronts work on the same class at (nearly) the same time: the
 // unrolled IPM of one class is ~80-130 KB of code, and wavefronts of different classes sharing a
 // CU's instruction cache measured 16 % slower (proportional class starts: 12.9 vs 11.1 ms, C4 path).
+template <bool ADV>
 __global__ __launch_bounds__(64) void k_cadmm(KArgs a) {
-  cadmm_drain<3, false>(a);
-  cadmm_drain<2, false>(a);
-  cadmm_drain<1, false>(a);
-  cadmm_drain<0, false>(a);
+  cadmm_drain<3, false, ADV>(a);
+  cadmm_drain<2, false, ADV>(a);
+  cadmm_drain<1, false, ADV>(a);
+  cadmm_drain<0, false, ADV>(a);
 }
 // The tail: the scenario-steps k_cadmm handed over (an agent QP not clean, or the tail rule) and, launched
 // concurrently with k_cadmm, those k_env_class routed here (wedged in a stall), one scenario per wavefront,
@@ -911,18 +951,19 @@ __global__ __launch_bounds__(64) void k_cadmm(KArgs a) {
 // start and stall exit of the tail rule's passes.  A kernel of its own: the robust solver compiled into k_cadmm
 // cost the fast path 36-60 % (register allocation, C4 A/B).  Without a listed scenario its blocks return at once.
 __global__ __launch_bounds__(64) void k_cadmm_tail(KArgs a) {
-  cadmm_drain<3, true>(a);
-  cadmm_drain<2, true>(a);
-  cadmm_drain<1, true>(a);
-  cadmm_drain<0, true>(a);
+  cadmm_drain<3, true, false>(a);
+  cadmm_drain<2, true, false>(a);
+  cadmm_drain<1, true, false>(a);
+  cadmm_drain<0, true, false>(a);
 }
 // Without a forest every scenario is in env class 0 (k_env_class finds no tree): the class-0 drain in a
 // kernel of its own, with a 960 B/lane scratch frame instead of k_cadmm's 1,728 (same arithmetic).  C5
 // 84.2 / 84.1 -> 80.3 / 79.9 ms per step, C2 12.7 / 12.9 -> 12.0 / 12.1 (round 4, kernel-trace A/B).
 // With a forest one launch per class measured 2x slower on C4 (each class launch drains to its own
 // tail): k_cadmm keeps the four drains in one launch there.
-__global__ __launch_bounds__(64) void k_cadmm0(KArgs a) { cadmm_drain<0, false>(a); }
-__global__ __launch_bounds__(64) void k_cadmm0_tail(KArgs a) { cadmm_drain<0, true>(a); }
+template <bool ADV>
+__global__ __launch_bounds__(64) void k_cadmm0(KArgs a) { cadmm_drain<0, false, ADV>(a); }
+__global__ __launch_bounds__(64) void k_cadmm0_tail(KArgs a) { cadmm_drain<0, true, false>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // DD: quasi-Newton matrix inverse per scenario (one 64-lane block per scenario)
@@ -1543,14 +1584,27 @@ __device__ inline void mountain_of(const KArgs& a, int sc, double* m) {
     for (int k = 0; k < DAT_MOUNTAIN_SIZE; ++k) m[k] = a.mountain[(size_t)f * DAT_MOUNTAIN_SIZE + k];
   }
 }
-template <bool LOG>
+// ADV (dat_kargs.hpp): the scenarios that take part.  The early pass runs beside the drain on the scenarios whose
+// done stamp is this step's and reads their f_des as the drain published it (write-through, past the caches); it
+// marks them in adv, and both passes count their scenarios (advcnt).  ADV_ALL compiles to the kernel without a gate.
+template <bool LOG, int ADV>
 __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, double dt, const double* fdes,
                                                        std::conditional_t<LOG, LogArgs, NoLog> lg) {
+  static_assert(!LOG || ADV == ADV_ALL, "the logging rollout is not gated");
   __shared__ double xs[64 * RO_X];
   const int n = a.n, G = 64 / n, NT = G * n;
   const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
   const int sc = blockIdx.x * G + ls;
-  const bool valid = lane < NT && sc < a.B;
+  bool valid = lane < NT && sc < a.B;
+  if constexpr (ADV != ADV_ALL) {
+    // (a scenario's lanes follow its first lane's reading of the stamp)
+    valid = __shfl((int)(valid && adv_gate<ADV, true>(a, sc)), (ls * n) & 63) != 0 && valid;
+    // (the stamp is read before the bytes it covers: the loads below are issued after this branch)
+    asm volatile("" ::: "memory");
+    const unsigned long long took = __ballot(valid && i == 0);
+    if (!took) return;  // no scenario of the block takes part (one wavefront: uniform)
+    if (lane == 0) atomicAdd(a.advcnt + (ADV == ADV_EARLY ? 0 : 1), (unsigned long long)__builtin_popcountll(took));
+  }
   const double* prm = valid ? prm_of(a, sc) : a.params;
   double* g = valid ? a.state + (size_t)sc * a.S : nullptr;
   double R[9], W[3], xl[3], vl[3], Rl[9], wl[3], fd[3];
@@ -1562,7 +1616,7 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
       xl[c] = g[DAT_S_XL(n) + c];
       vl[c] = g[DAT_S_VL(n) + c];
       wl[c] = g[DAT_S_WL(n) + c];
-      fd[c] = fdes[(size_t)sc * 3 * n + 3 * i + c];
+      fd[c] = ADV == ADV_EARLY ? ld_wt(fdes + (size_t)sc * 3 * n + 3 * i + c) : fdes[(size_t)sc * 3 * n + 3 * i + c];
     }
     cnt = a.counter[sc];
   }
@@ -1720,18 +1774,26 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
       }
       for (int k = 0; k < 9; ++k) g[DAT_S_RL(n) + k] = Rl[k];
       a.counter[sc] = cnt;
+      if constexpr (ADV == ADV_EARLY) a.adv[sc] = a.serial;
     }
   }
 }
 
 // lg: the open log's arguments at this launch (dat_closed_loop), or null: the plain kernel
+// adv: the pass of the closed loop's advance overlap (ADV_ALL: every scenario)
 void launch_rollout(const KArgs& a, int B, hipStream_t stream, int steps, double dt, const double* fdes,
-                    const LogArgs* lg = nullptr) {
+                    const LogArgs* lg = nullptr, int adv = ADV_ALL) {
   const int G = 64 / a.n;
+  const dim3 grid((B + G - 1) / G);
+  constexpr auto k_log = k_rollout_agents<true, ADV_ALL>;
+  constexpr auto k_all = k_rollout_agents<false, ADV_ALL>;
+  constexpr auto k_early = k_rollout_agents<false, ADV_EARLY>;
+  constexpr auto k_rest = k_rollout_agents<false, ADV_REST>;
   if (lg)
-    hipLaunchKernelGGL(k_rollout_agents<true>, dim3((B + G - 1) / G), dim3(64), 0, stream, a, steps, dt, fdes, *lg);
+    hipLaunchKernelGGL(k_log, grid, dim3(64), 0, stream, a, steps, dt, fdes, *lg);
   else
-    hipLaunchKernelGGL(k_rollout_agents<false>, dim3((B + G - 1) / G), dim3(64), 0, stream, a, steps, dt, fdes, NoLog{});
+    hipLaunchKernelGGL(adv == ADV_EARLY ? k_early : adv == ADV_REST ? k_rest : k_all, grid, dim3(64), 0, stream, a,
+                       steps, dt, fdes, NoLog{});
 }
 
 // RQPLowLevelController.control (control/rqp_centralized.py:518-535) at the current states: thrust
@@ -1760,9 +1822,10 @@ __global__ void k_rp_rollout(KArgs a, int steps, double dt, const double* f) {
   a.counter[sc] = cnt;
 }
 
+template <int ADV>
 __global__ void k_desired(KArgs a, double* acc) {
   const int sc = blockIdx.x * blockDim.x + threadIdx.x;
-  if (sc >= a.B) return;
+  if (sc >= a.B || !adv_gate<ADV, false>(a, sc)) return;
   const double* st = a.state + (size_t)sc * a.S;
   double* o = acc + (size_t)sc * 6;
   double m[DAT_MOUNTAIN_SIZE];
@@ -2011,6 +2074,17 @@ struct dat_handle {
   hipStream_t tail_stream = nullptr;  // C-ADMM, one sub-batch: the tail-routed scenarios' launch beside k_cadmm
   hipEvent_t tail_ev[2] = {};
   double* wrec = nullptr;  // C-ADMM: the tail's warm-start records (B n WREC_SIZE)
+  // C-ADMM closed loop, one sub-batch, no log: the rollout and next env rows of the scenarios the drain has finished
+  // run beside its ramp-down on a stream of their own (closed_loop_overlap; dat_set_advance_overlap)
+  bool adv_on = true;
+  int serial = 0;                      // closed-loop steps of the handle so far: the step's stamp
+  int *done = nullptr, *adv = nullptr;  // [B] stamps: KArgs::done, KArgs::adv
+  int* qempty = nullptr;                // the mapped host word of KArgs::qempty, and its device address
+  int* qempty_dev = nullptr;
+  unsigned long long* advcnt = nullptr;  // KArgs::advcnt
+  unsigned char* advmask = nullptr;      // dat_debug_advance_split: device copy of the mask (null: not set)
+  hipStream_t adv_stream = nullptr;      // created on first use, like the tail stream
+  hipEvent_t adv_ev = nullptr;
   double agent_qp_ms = 0.0;  // device time of the last dat_solve_agent_qp_batch launch
   int ll_kind = 0;  // LL_PD (example/rqp_example.py:113) or LL_SM
   std::vector<void*> allocs;
@@ -2138,9 +2212,15 @@ size_t dd_setup_lds(int n) {
 // tail stream, started with k_cadmm (their lists are known after k_bucket), and the hand-over lists after
 // k_cadmm on the step's stream, which then waits for the first.
 constexpr int TAIL_BLOCKS = 256;
+// (KArgs::done set: the ADV instantiations, closed_loop_overlap)
 int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st) {
   KArgs r = a;
   r.G = 1;
+  const bool adv = a.done != nullptr;
+  const auto kc = adv ? k_cadmm<true> : k_cadmm<false>;
+  const auto kt = k_cadmm_tail;
+  const auto kc0 = adv ? k_cadmm0<true> : k_cadmm0<false>;
+  const auto kt0 = k_cadmm0_tail;
   if (h->nforest > 0) {
     if (a.route) {
       KArgs t = r;
@@ -2148,17 +2228,26 @@ int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st
       const hipStream_t ts = h->tail_stream;
       HIPCHK(hipEventRecord(h->tail_ev[0], st));
       HIPCHK(hipStreamWaitEvent(ts, h->tail_ev[0], 0));
-      hipLaunchKernelGGL(k_cadmm_tail, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(a.n, NCLS - 1), ts, t);
+      hipLaunchKernelGGL(kt, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(a.n, NCLS - 1), ts, t);
       HIPCHK(hipEventRecord(h->tail_ev[1], ts));
     }
-    hipLaunchKernelGGL(k_cadmm, dim3(blocks), dim3(64), cadmm_lds_bytes(a.n, a.G, NCLS - 1), st, a);
-    hipLaunchKernelGGL(k_cadmm_tail, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(r.n, NCLS - 1), st, r);
+    hipLaunchKernelGGL(kc, dim3(blocks), dim3(64), cadmm_lds_bytes(a.n, a.G, NCLS - 1), st, a);
+    hipLaunchKernelGGL(kt, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(r.n, NCLS - 1), st, r);
     if (a.route) HIPCHK(hipStreamWaitEvent(st, h->tail_ev[1], 0));
   } else {
-    hipLaunchKernelGGL(k_cadmm0, dim3(blocks), dim3(64), cadmm_lds_bytes(a.n, a.G, 0), st, a);
-    hipLaunchKernelGGL(k_cadmm0_tail, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(r.n, 0), st, r);
+    hipLaunchKernelGGL(kc0, dim3(blocks), dim3(64), cadmm_lds_bytes(a.n, a.G, 0), st, a);
+    hipLaunchKernelGGL(kt0, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(r.n, 0), st, r);
   }
   return 0;
+}
+
+// C-ADMM, the whole batch on the handle's stream: the class sort of the step's keys (k_env_class), the event ek, the drain
+int launch_sort_drain(const dat_handle* h, const KArgs& a) {
+  const int B = h->cfg.batch;
+  hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, h->stream, B, (const int*)h->need, h->slist, h->scount);
+  HIPCHK(hipEventRecord(h->ek, h->stream));
+  const int Gc = a.G, cblocks = (B + Gc - 1) / Gc;
+  return launch_cadmm(h, a, std::min(cblocks, h->persistent_blocks), h->stream);
 }
 
 // ksteps > 1 (dat_control_steps): that many control steps fused into one drain, acc_seq ksteps x B x 6
@@ -2174,11 +2263,8 @@ int launch_hl(dat_handle* h, int ksteps = 1, const double* acc_seq = nullptr) {
   if (h->cfg.mode == DAT_MODE_CADMM) {
     int G = 64 / n;
     int blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL(k_env_class, dim3(blocks), dim3(64), 0, h->stream, a);
-    hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, h->stream, B, (const int*)h->need, h->slist, h->scount);
-    HIPCHK(hipEventRecord(h->ek, h->stream));
-    const int Gc = a.G, cblocks = (B + Gc - 1) / Gc;
-    if (launch_cadmm(h, a, std::min(cblocks, h->persistent_blocks), h->stream)) return -1;
+    hipLaunchKernelGGL(k_env_class<ADV_ALL>, dim3(blocks), dim3(64), 0, h->stream, a);
+    if (launch_sort_drain(h, a)) return -1;
   } else if (h->cfg.mode == DAT_MODE_DD) {
     if (n > DD_REG_NMAX)  // [H | I] in LDS: beyond the default 64 KB dynamic LDS from n = 11 on
       HIPCHK(hipFuncSetAttribute((const void*)k_dd_setup<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2416,6 +2502,17 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
     rc |= dalloc(h, &h->rres, B * RRES_INTS);
     rc |= dalloc(h, &h->rlist, B);
     rc |= dalloc(h, &h->wrec, B * n * WREC_SIZE);
+    rc |= dalloc(h, &h->done, B);
+    rc |= dalloc(h, &h->adv, B);
+    rc |= dalloc(h, &h->advcnt, 2);
+    // (without the host word the closed loop keeps the serial schedule)
+    if (hipHostMalloc((void**)&h->qempty, sizeof(int), hipHostMallocMapped) == hipSuccess) {
+      *h->qempty = 0;
+      if (hipHostGetDevicePointer((void**)&h->qempty_dev, h->qempty, 0) != hipSuccess) h->qempty_dev = nullptr;
+    } else {
+      h->qempty = nullptr;
+      (void)hipGetLastError();
+    }
   } else if (c.mode == DAT_MODE_DD) {
     rc |= dalloc(h, &h->need, B);
     rc |= dalloc(h, &h->ipmx, B);
@@ -2489,6 +2586,13 @@ int dat_destroy(dat_handle* h) {
   }
   for (int e = 0; e < 2; ++e)
     if (h->tail_ev[e]) (void)hipEventDestroy(h->tail_ev[e]);
+  if (h->adv_stream) {
+    (void)hipStreamSynchronize(h->adv_stream);
+    (void)hipStreamDestroy(h->adv_stream);
+  }
+  if (h->adv_ev) (void)hipEventDestroy(h->adv_ev);
+  if (h->advmask) (void)hipFree(h->advmask);
+  if (h->qempty) (void)hipHostFree(h->qempty);
   if (h->ev_start) (void)hipEventDestroy(h->ev_start);
   if (h->ev_end) (void)hipEventDestroy(h->ev_end);
   for (hipEvent_t e : h->sub_ev) (void)hipEventDestroy(e);
@@ -2635,7 +2739,7 @@ int dat_control_step(dat_handle* h, const double* state, const double* acc_des, 
   if (acc_des) {
     HIPCHK(hipMemcpyAsync(h->acc, acc_des, sizeof(double) * B * 6, hipMemcpyHostToDevice, h->stream));
   } else {
-    hipLaunchKernelGGL(k_desired, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
+    hipLaunchKernelGGL(k_desired<ADV_ALL>, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
     HIPCHK(hipGetLastError());
   }
   if (launch_hl(h)) return -1;
@@ -2716,9 +2820,9 @@ int closed_loop_sub(dat_handle* h, int hl_steps) {
       const int off = (int)((long long)B * s / S), Bs = (int)((long long)B * (s + 1) / S) - off;
       hipStream_t st = h->sub_stream[s];
       KArgs a = sub_kargs(h, off, Bs, s);
-      hipLaunchKernelGGL(k_desired, dim3((Bs + 63) / 64), dim3(64), 0, st, a, (double*)a.acc);
+      hipLaunchKernelGGL(k_desired<ADV_ALL>, dim3((Bs + 63) / 64), dim3(64), 0, st, a, (double*)a.acc);
       const int G = 64 / n;
-      hipLaunchKernelGGL(k_env_class, dim3((Bs + G - 1) / G), dim3(64), 0, st, a);
+      hipLaunchKernelGGL(k_env_class<ADV_ALL>, dim3((Bs + G - 1) / G), dim3(64), 0, st, a);
       hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, st, Bs, (const int*)a.need, a.slist, a.scount);
       const hipEvent_t* ev = h->sub_ev.data() + 2 * ((size_t)k * S + s);
       HIPCHK(hipEventRecord(ev[0], st));
@@ -2758,12 +2862,118 @@ int closed_loop_sub(dat_handle* h, int hl_steps) {
   return 0;
 }
 
+// Does dat_closed_loop run the advance overlap?  C-ADMM on one sub-batch with no log open, the switch on, and the
+// advance stream, its event and the host word in place (the stream is created on first use, like the tail stream:
+// three streams with it, within the four hardware queues).  Otherwise the serial schedule, same results.
+bool advance_ready(dat_handle* h) {
+  if (!h->adv_on || h->cfg.mode != DAT_MODE_CADMM || h->nsub != 1 || h->log.open) return false;
+  if (!h->qempty || !h->qempty_dev || !h->done || !h->adv || !h->advcnt) return false;
+  if (!h->adv_stream) {
+    if (hipStreamCreateWithFlags(&h->adv_stream, hipStreamNonBlocking) != hipSuccess) {
+      h->adv_stream = nullptr;
+      (void)hipGetLastError();
+      return false;
+    }
+  }
+  if (!h->adv_ev && hipEventCreateWithFlags(&h->adv_ev, hipEventDisableTiming) != hipSuccess) {
+    h->adv_ev = nullptr;
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+
+// The closed loop with the advance overlap.  Per step the chain is the serial schedule's -- class sort, drain,
+// rollout, desired acceleration, env rows -- but the last three run in two passes over disjoint scenarios: `early`
+// on the advance stream beside the drain's ramp-down, on the scenarios whose done stamp is the step's, started when
+// k_cadmm's class-0 queue has been claimed empty (the host word) or the drain has ended; `rest` on the handle's
+// stream after the drain, on the others.  A scenario's step is the same sequence of the same device functions on
+// the same inputs in either pass.  The desired acceleration and env rows of a call's first step are computed for
+// every scenario up front, and none are computed after its last step (the next call starts from the state alone,
+// which dat_set_state may replace).
+// What the early pass may touch while the drain runs: a finished scenario's state, acc, env rows / mask, sort key
+// and rotation counter are read by the drain only when a slot takes the scenario (the refill; ksteps == 1 here),
+// so they may be overwritten; its f_des, iters and ipmx were stored write-through before the stamp and are read
+// past the caches; everything else the early kernels read dates from before the drain's launch.
+int closed_loop_overlap(dat_handle* h, int hl_steps) {
+  const int B = h->cfg.batch, n = h->cfg.n;
+  if (!h->have_params) return fail("dat_set_params has not been called");
+  KArgs a = kargs(h);
+  a.done = h->done;
+  a.adv = h->adv;
+  a.qempty = h->qempty_dev;
+  a.advmask = h->advmask;
+  a.advcnt = h->advcnt;
+  auto now_ms = [] {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  };
+  const int Ge = 64 / n;
+  const dim3 gd((B + 63) / 64), ge((B + Ge - 1) / Ge);
+  // the passes' kernels after the drain of step s: rollout, then (not after the call's last step) the next step's
+  // desired acceleration and env rows
+  auto advance = [&](hipStream_t st, int mode, bool next) {
+    launch_rollout(a, B, st, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes, nullptr, mode);
+    if (!next) return;
+    if (mode == ADV_EARLY) {
+      hipLaunchKernelGGL(k_desired<ADV_EARLY>, gd, dim3(64), 0, st, a, h->acc);
+      hipLaunchKernelGGL(k_env_class<ADV_EARLY>, ge, dim3(64), 0, st, a);
+    } else {
+      hipLaunchKernelGGL(k_desired<ADV_REST>, gd, dim3(64), 0, st, a, h->acc);
+      hipLaunchKernelGGL(k_env_class<ADV_REST>, ge, dim3(64), 0, st, a);
+    }
+  };
+  h->marks.clear();
+  h->marks.push_back(now_ms());
+  for (int s = 0; s < hl_steps; ++s) {
+    if (h->cfg.record_err && h->err)
+      HIPCHK(hipMemsetAsync(h->err, 0xff, sizeof(double) * (size_t)B * (h->cfg.max_iter + 1), h->stream));  // NaN pad
+    HIPCHK(hipEventRecord(h->e0, h->stream));
+    if (s == 0) {
+      hipLaunchKernelGGL(k_desired<ADV_ALL>, gd, dim3(64), 0, h->stream, a, h->acc);
+      hipLaunchKernelGGL(k_env_class<ADV_ALL>, ge, dim3(64), 0, h->stream, a);
+    }
+    h->serial = h->serial == INT_MAX ? 1 : h->serial + 1;  // (0: the arrays' initial value, no step's stamp)
+    a.serial = h->serial;
+    if (launch_sort_drain(h, a)) return -1;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->e1, h->stream));
+    // host only: until the queue-empty word carries the step's serial, at the latest until the drain has ended
+    // (dat_debug_advance_split: always until then, so that every scenario's stamp is in place and the mask alone
+    // decides the split)
+    const volatile int* const qe = h->qempty;
+    for (;;) {
+      bool hit = false;
+      for (int k = 0; k < 256 && !hit; ++k) hit = !h->advmask && *qe == a.serial;
+      if (hit) break;
+      const hipError_t q = hipEventQuery(h->e1);
+      if (q == hipSuccess) break;
+      if (q != hipErrorNotReady) HIPCHK(q);
+    }
+    (void)hipGetLastError();  // (a not-ready query is no error of the loop's)
+    const bool next = s + 1 < hl_steps;
+    advance(h->adv_stream, ADV_EARLY, next);
+    HIPCHK(hipEventRecord(h->adv_ev, h->adv_stream));
+    // (enqueued before the wait for the drain, so that its end finds them in the queue)
+    HIPCHK(hipStreamWaitEvent(h->stream, h->adv_ev, 0));
+    advance(h->stream, ADV_REST, next);
+    HIPCHK(hipGetLastError());
+    if (finish_hl(h)) return -1;
+    h->marks.push_back(now_ms());
+  }
+  return 0;
+}
+
 int dat_closed_loop(dat_handle* h, int hl_steps) {
   if (!h) return fail("null handle");
   if (log_admit(h, hl_steps)) return -1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->nsub > 1) {
     if (closed_loop_sub(h, hl_steps)) return -1;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  }
+  if (advance_ready(h)) {
+    if (closed_loop_overlap(h, hl_steps)) return -1;
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
   }
@@ -2775,7 +2985,7 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
   h->marks.clear();
   h->marks.push_back(now_ms());
   for (int s = 0; s < hl_steps; ++s) {
-    hipLaunchKernelGGL(k_desired, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
+    hipLaunchKernelGGL(k_desired<ADV_ALL>, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
     if (launch_hl(h)) return -1;
     if (h->log.open) {
       const LogArgs lg = log_args(h);
@@ -2872,6 +3082,7 @@ int dat_reset_counters(dat_handle* h) {
     static const unsigned long long inf = dist_key(HUGE_VAL);
     HIPCHK(hipMemcpyAsync(h->counters + CNT_COLL + 1, &inf, sizeof(inf), hipMemcpyHostToDevice, h->stream));
   }
+  if (h->advcnt) HIPCHK(hipMemsetAsync(h->advcnt, 0, 2 * sizeof(unsigned long long), h->stream));
   h->cadmm_ms = 0.0;
   HIPCHK(hipStreamSynchronize(h->stream));
   h->hl_steps = 0;
@@ -2894,6 +3105,40 @@ int dat_set_sub_batches(dat_handle* h, int count) {
   if (!h->ev_start) HIPCHK(hipEventCreate(&h->ev_start));
   if (!h->ev_end) HIPCHK(hipEventCreate(&h->ev_end));
   h->nsub = count;
+  return 0;
+}
+
+int dat_set_advance_overlap(dat_handle* h, int on) {
+  if (!h) return fail("null handle");
+  h->adv_on = on != 0;
+  return 0;
+}
+
+int dat_get_advance_counts(dat_handle* h, long long* early, long long* late) {
+  if (!h) return fail("null handle");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  unsigned long long c[2] = {0, 0};
+  if (h->advcnt) {
+    HIPCHK(hipMemcpyAsync(c, h->advcnt, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  if (early) *early = (long long)c[0];
+  if (late) *late = (long long)c[1];
+  return 0;
+}
+
+int dat_debug_advance_split(dat_handle* h, const unsigned char* early_mask) {
+  if (!h) return fail("null handle");
+  if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_debug_advance_split: C-ADMM handles only");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!early_mask) {
+    if (h->advmask) (void)hipFree(h->advmask);
+    h->advmask = nullptr;
+    return 0;
+  }
+  if (!h->advmask) HIPCHK(hipMalloc((void**)&h->advmask, (size_t)h->cfg.batch));
+  HIPCHK(hipMemcpy(h->advmask, early_mask, (size_t)h->cfg.batch, hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -119,7 +119,39 @@ struct KArgs {
   int tail_prev, tail_pass;      // C-ADMM: the tail rule (TAIL_PREV / TAIL_PASS with a forest, INT_MAX without)
   int route;                     // C-ADMM, one sub-batch: wedged scenarios go to the tail before the step (k_env_class)
   int tmode;                     // k_cadmm_tail: 0 the hand-over lists (rlist), 1 the tail-routed stretch of slist
+  // The closed loop's advance overlap (dat_set_advance_overlap; done null: off, plain stores, no stamps).
+  int serial;                    // the handle's count of closed-loop steps, this step's stamp: never repeats
+  int* done;                     // [B] the drain: serial of the step whose fdes / iters / ipmx are published
+  int* adv;                      // [B] the early rollout: serial of the step it has advanced the scenario through
+  int* qempty;                   // one word of mapped host memory: serial, once k_cadmm's class-0 queue is claimed empty
+  const unsigned char* advmask;  // dat_debug_advance_split: a done stamp counts only where the mask is set (null: all)
+  unsigned long long* advcnt;    // scenario-steps advanced by the [0] early, [1] rest pass
 };
+
+// Modes of the gated kernels (k_rollout_agents, k_desired, k_env_class): which scenarios of the grid take part
+constexpr int ADV_ALL = 0;    // every scenario: the kernel without any gate
+constexpr int ADV_EARLY = 1;  // beside the running drain: the rollout where done[sc] == serial (it sets adv[sc] =
+                              // serial), k_desired and k_env_class where adv[sc] == serial
+constexpr int ADV_REST = 2;   // after the drain: where adv[sc] != serial
+
+// Write-through store and its load (global_store / global_load ... sc1): what a kernel publishes to another kernel
+// that runs beside it.  The address is a global one by construction (never a flat access).
+template <class T>
+__device__ __forceinline__ void st_wt(T* p, T v) {
+  __hip_atomic_store((__attribute__((address_space(1))) T*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <class T>
+__device__ __forceinline__ T ld_wt(const T* p) {
+  return __hip_atomic_load((const __attribute__((address_space(1))) T*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Does scenario sc take part in a kernel of mode ADV?  (k_desired, k_env_class: early through adv, the rollout's mark)
+template <int ADV, bool ROLLOUT>
+__device__ __forceinline__ bool adv_gate(const KArgs& a, int sc) {
+  if constexpr (ADV == ADV_ALL) return true;
+  if constexpr (ADV == ADV_REST) return a.adv[sc] != a.serial;
+  if constexpr (!ROLLOUT) return a.adv[sc] == a.serial;
+  return ld_wt(a.done + sc) == a.serial && (a.advmask == nullptr || a.advmask[sc] != 0);
+}
 
 // The closed loop's recorder (dat_log_*), handed to k_rollout_agents<true> at every HL step: where the records
 // go and the log clock at the launch.  Record layouts: dat_layout.h (DAT_LOG_*).  A launch writes the HL record

@@ -150,6 +150,20 @@ int dat_closed_loop(dat_handle* h, int hl_steps);
  * shared by all streams) the drain hands them to the tail kernel before their first pass -- the same passes,
  * the same results. */
 int dat_set_sub_batches(dat_handle* h, int count);
+/* C-ADMM closed loop on one sub-batch with no log open: the advance overlap (default on).  Once the drain's last
+ * queue has been claimed empty, the rollout of the scenarios it has finished, and their next step's desired
+ * acceleration and env rows, run on a stream of their own beside the drain's ramp-down ("early"); the others
+ * follow after the drain ("late").  A scenario's arithmetic is the same in either pass and every result is
+ * bitwise that of the serial schedule (on = 0), which sub-batches, an open log, the other modes and the
+ * step-by-step entry points keep. */
+int dat_set_advance_overlap(dat_handle* h, int on);
+/* Scenario-steps advanced by the early and by the late pass of the advance overlap since the last counter
+ * reset; their sum is batch x HL steps run under the overlap (both 0 where the serial schedule ran). */
+int dat_get_advance_counts(dat_handle* h, long long* early, long long* late);
+/* Test hook: while a mask (batch bytes) is set, dat_closed_loop starts the early pass only after the drain has
+ * ended and lets it take exactly the scenarios with early_mask[sc] != 0: a split between the two passes that
+ * does not depend on timing.  Null clears it. */
+int dat_debug_advance_split(dat_handle* h, const unsigned char* early_mask);
 /* Host steady-clock marks (ms) of the last dat_closed_loop call: [0] its start (0.0), then the completion
  * of each HL step's control kernel; consecutive differences are per-step times of the back-to-back run.
  * Writes up to max_marks values; returns the number of marks (hl_steps + 1).  With sub-batch streams
