@@ -573,7 +573,7 @@ __device__ __forceinline__ void flush_solve_counters(const KArgs& a, unsigned lo
 // the previous pass and the stall exit (ipm_solve WS).  Built with -ffp-contract=on (multiply-adds fused within
 // an expression only), the inlined fast solver computes the same bits in either kernel, and the tail rule
 // depends on the scenario's own history: a scenario's results do not depend on which kernel ran which pass.
-// ADV: the drain of the closed loop's advance overlap (closed_loop_overlap): a stopped scenario's f_des, iters and
+// ADV: the drain of the closed loop's advance overlap (dat_closed_loop): a stopped scenario's f_des, iters and
 // ipmx are stored write-through and stamped in KArgs::done, and k_cadmm's class-0 drain tells the host when its
 // queue has been claimed empty.  Without it k_cadmm / k_cadmm0 are compiled without any of that; the tail kernels
 // exist once and go by KArgs::done at run time (a second instantiation changes how their solver is inlined).
@@ -2023,6 +2023,13 @@ struct dat_log {
   long long hl_count(int hl_every) const { return clock / hl_every - hl_base; }
   long long step_count() const { return (clock + log_every - 1) / log_every - step_base; }
 };
+// A side stream of the handle with its untimed events, made on first use, whole or not at all (side_get: st set
+// means ready).  A stream made at dat_create would take one of the box's GPU_MAX_HW_QUEUES = 4 hardware queues
+// from the sub-batch streams.
+struct side_stream {
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {};
+};
 struct dat_handle {
   dat_log log;
   dat_config cfg;
@@ -2066,16 +2073,14 @@ struct dat_handle {
   // C-ADMM closed loop on sub-batches (dat_set_sub_batches): contiguous scenario ranges, each with its own
   // stream, so one sub-batch's kernels fill the drain tail and the short kernels of the others
   int nsub = 1;
-  std::vector<hipEvent_t> sub_ev;  // closed_loop_sub: k_cadmm start / end events per sub-batch and step
-  hipStream_t sub_stream[DAT_MAX_SUB] = {};
-  hipEvent_t sub_done[DAT_MAX_SUB] = {};
+  side_stream sub[DAT_MAX_SUB];    // [0].st: the handle's stream; ev[0]: the sub-batch's end, joined into that stream
+  std::vector<hipEvent_t> sub_ev;  // dat_closed_loop on sub-batches: k_cadmm start / end events per step and sub-batch
   hipEvent_t ev_start = nullptr, ev_end = nullptr;
-  // C-ADMM with a forest: per sub-batch the stream of the concurrent tail launch and its start / end events
-  hipStream_t tail_stream = nullptr;  // C-ADMM, one sub-batch: the tail-routed scenarios' launch beside k_cadmm
-  hipEvent_t tail_ev[2] = {};
+  // C-ADMM with a forest, one sub-batch: the tail-routed scenarios' launch beside k_cadmm, its start / end events
+  side_stream tail;
   double* wrec = nullptr;  // C-ADMM: the tail's warm-start records (B n WREC_SIZE)
   // C-ADMM closed loop, one sub-batch, no log: the rollout and next env rows of the scenarios the drain has finished
-  // run beside its ramp-down on a stream of their own (closed_loop_overlap; dat_set_advance_overlap)
+  // run beside its ramp-down on a stream of their own (dat_closed_loop's overlap; dat_set_advance_overlap)
   bool adv_on = true;
   int serial = 0;                      // closed-loop steps of the handle so far: the step's stamp
   int *done = nullptr, *adv = nullptr;  // [B] stamps: KArgs::done, KArgs::adv
@@ -2083,11 +2088,13 @@ struct dat_handle {
   int* qempty_dev = nullptr;
   unsigned long long* advcnt = nullptr;  // KArgs::advcnt
   unsigned char* advmask = nullptr;      // dat_debug_advance_split: device copy of the mask (null: not set)
-  hipStream_t adv_stream = nullptr;      // created on first use, like the tail stream
-  hipEvent_t adv_ev = nullptr;
+  side_stream advance;                   // the early pass's stream; ev[0]: its end, joined into the handle's stream
   double agent_qp_ms = 0.0;  // device time of the last dat_solve_agent_qp_batch launch
   int ll_kind = 0;  // LL_PD (example/rqp_example.py:113) or LL_SM
+  // what the handle owns: dat_destroy frees by list
   std::vector<void*> allocs;
+  std::vector<hipStream_t> streams;
+  std::vector<hipEvent_t> events;
 };
 
 // C-ADMM scenario slots per k_cadmm wavefront: floor(64/n), fewer when the batch would not give
@@ -2121,7 +2128,40 @@ void dfree(dat_handle* h, void* p) {
   (void)hipFree(p);
 }
 
-KArgs kargs(dat_handle* h) {
+// a timed event of the handle's, made on first use
+hipError_t own_event(dat_handle* h, hipEvent_t* e) {
+  if (*e) return hipSuccess;
+  const hipError_t r = hipEventCreate(e);
+  if (r == hipSuccess) h->events.push_back(*e);
+  return r;
+}
+
+// The side stream *s with nev events: got, or made on first use.  A failure leaves *s empty and no sticky error:
+// the caller falls back (no tail routing, the serial schedule) or reports it.
+hipError_t side_get(dat_handle* h, side_stream* s, int nev) {
+  if (s->st) return hipSuccess;
+  side_stream t;
+  hipError_t e = hipStreamCreateWithFlags(&t.st, hipStreamNonBlocking);
+  for (int k = 0; k < nev && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&t.ev[k], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    for (hipEvent_t v : t.ev)
+      if (v) (void)hipEventDestroy(v);
+    if (t.st) (void)hipStreamDestroy(t.st);
+    (void)hipGetLastError();
+    return e;
+  }
+  h->streams.push_back(t.st);
+  h->events.insert(h->events.end(), t.ev, t.ev + nev);
+  *s = t;
+  return hipSuccess;
+}
+
+// The concurrent tail launch needs a stream of its own beside the step's: with sub-batches (4 streams) a fifth and
+// more would share the hardware queues with them and serialise the sub-batches.
+bool tail_wanted(const dat_handle* h) { return h->cfg.mode == DAT_MODE_CADMM && h->nforest > 0 && h->nsub == 1; }
+
+// the handle as kernel arguments: a projection, nothing is created (the tail stream: step_entry)
+KArgs kargs(const dat_handle* h) {
   KArgs a;
   memset(&a, 0, sizeof(a));
   const dat_config& c = h->cfg;
@@ -2177,15 +2217,7 @@ KArgs kargs(dat_handle* h) {
   a.wrec = h->wrec;
   a.tail_prev = h->nforest > 0 ? TAIL_PREV : INT_MAX;
   a.tail_pass = h->nforest > 0 ? TAIL_PASS : INT_MAX;
-  // the concurrent tail launch needs a stream of its own beside the step's: with sub-batches (4 streams) a fifth
-  // and more would share the box's GPU_MAX_HW_QUEUES = 4 hardware queues with them and serialise the sub-batches
-  a.route = h->cfg.mode == DAT_MODE_CADMM && h->nforest > 0 && h->nsub == 1;
-  // (created on first use: a stream made at dat_create would take a hardware queue from the sub-batch streams)
-  if (a.route && !h->tail_stream &&
-      (hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking) != hipSuccess ||
-       hipEventCreateWithFlags(&h->tail_ev[0], hipEventDisableTiming) != hipSuccess ||
-       hipEventCreateWithFlags(&h->tail_ev[1], hipEventDisableTiming) != hipSuccess))
-    a.route = 0;  // (no stream: the wedged scenarios go through k_cadmm's hand-over, same results)
+  a.route = tail_wanted(h) && h->tail.st;  // (no stream: the wedged scenarios go through k_cadmm's hand-over, same results)
   a.tmode = 0;
 #ifdef DAT_NO_TAIL  // A/B builds only (tools/build_var.sh): the round-5 schedule, no tail rule
   a.tail_prev = a.tail_pass = INT_MAX;
@@ -2212,7 +2244,7 @@ size_t dd_setup_lds(int n) {
 // tail stream, started with k_cadmm (their lists are known after k_bucket), and the hand-over lists after
 // k_cadmm on the step's stream, which then waits for the first.
 constexpr int TAIL_BLOCKS = 256;
-// (KArgs::done set: the ADV instantiations, closed_loop_overlap)
+// (KArgs::done set: the ADV instantiations, dat_closed_loop's overlap)
 int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st) {
   KArgs r = a;
   r.G = 1;
@@ -2225,15 +2257,15 @@ int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st
     if (a.route) {
       KArgs t = r;
       t.tmode = 1;
-      const hipStream_t ts = h->tail_stream;
-      HIPCHK(hipEventRecord(h->tail_ev[0], st));
-      HIPCHK(hipStreamWaitEvent(ts, h->tail_ev[0], 0));
+      const hipStream_t ts = h->tail.st;
+      HIPCHK(hipEventRecord(h->tail.ev[0], st));
+      HIPCHK(hipStreamWaitEvent(ts, h->tail.ev[0], 0));
       hipLaunchKernelGGL(kt, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(a.n, NCLS - 1), ts, t);
-      HIPCHK(hipEventRecord(h->tail_ev[1], ts));
+      HIPCHK(hipEventRecord(h->tail.ev[1], ts));
     }
     hipLaunchKernelGGL(kc, dim3(blocks), dim3(64), cadmm_lds_bytes(a.n, a.G, NCLS - 1), st, a);
     hipLaunchKernelGGL(kt, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(r.n, NCLS - 1), st, r);
-    if (a.route) HIPCHK(hipStreamWaitEvent(st, h->tail_ev[1], 0));
+    if (a.route) HIPCHK(hipStreamWaitEvent(st, h->tail.ev[1], 0));
   } else {
     hipLaunchKernelGGL(kc0, dim3(blocks), dim3(64), cadmm_lds_bytes(a.n, a.G, 0), st, a);
     hipLaunchKernelGGL(kt0, dim3(TAIL_BLOCKS), dim3(64), cadmm_tail_lds_bytes(r.n, 0), st, r);
@@ -2241,66 +2273,32 @@ int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st
   return 0;
 }
 
-// C-ADMM, the whole batch on the handle's stream: the class sort of the step's keys (k_env_class), the event ek, the drain
-int launch_sort_drain(const dat_handle* h, const KArgs& a) {
-  const int B = h->cfg.batch;
-  hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, h->stream, B, (const int*)h->need, h->slist, h->scount);
-  HIPCHK(hipEventRecord(h->ek, h->stream));
-  const int Gc = a.G, cblocks = (B + Gc - 1) / Gc;
-  return launch_cadmm(h, a, std::min(cblocks, h->persistent_blocks), h->stream);
-}
-
-// ksteps > 1 (dat_control_steps): that many control steps fused into one drain, acc_seq ksteps x B x 6
-int launch_hl(dat_handle* h, int ksteps = 1, const double* acc_seq = nullptr) {
-  KArgs a = kargs(h);
-  a.ksteps = ksteps;
-  if (acc_seq) a.acc = acc_seq;
-  const int n = h->cfg.n, B = h->cfg.batch;
-  if (!h->have_params) return fail("dat_set_params has not been called");
-  if (h->cfg.record_err && h->err)
-    HIPCHK(hipMemsetAsync(h->err, 0xff, sizeof(double) * (size_t)B * (h->cfg.max_iter + 1), h->stream));  // NaN pad
-  HIPCHK(hipEventRecord(h->e0, h->stream));
-  if (h->cfg.mode == DAT_MODE_CADMM) {
-    int G = 64 / n;
-    int blocks = (B + G - 1) / G;
-    hipLaunchKernelGGL(k_env_class<ADV_ALL>, dim3(blocks), dim3(64), 0, h->stream, a);
-    if (launch_sort_drain(h, a)) return -1;
-  } else if (h->cfg.mode == DAT_MODE_DD) {
-    if (n > DD_REG_NMAX)  // [H | I] in LDS: beyond the default 64 KB dynamic LDS from n = 11 on
-      HIPCHK(hipFuncSetAttribute((const void*)k_dd_setup<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)dd_setup_lds(n)));
-    switch (n <= DD_REG_NMAX ? n : 0) {
-      case 3: hipLaunchKernelGGL(k_dd_setup<3>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-      case 4: hipLaunchKernelGGL(k_dd_setup<4>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-      case 5: hipLaunchKernelGGL(k_dd_setup<5>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-      case 6: hipLaunchKernelGGL(k_dd_setup<6>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-      case 7: hipLaunchKernelGGL(k_dd_setup<7>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-      case 8: hipLaunchKernelGGL(k_dd_setup<8>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-      default: hipLaunchKernelGGL(k_dd_setup<0>, dim3(B), dim3(64), dd_setup_lds(n), h->stream, a); break;
-    }
-    hipLaunchKernelGGL(k_dd_key, dim3((B + 63) / 64), dim3(64), 0, h->stream, a);
-    hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, h->stream, B, (const int*)h->need, h->slist, h->scount);
-    HIPCHK(hipEventRecord(h->ek, h->stream));
-    int G = 64 / n;
-    int blocks = (B + G - 1) / G;
-    if (h->nforest > 0)
-      hipLaunchKernelGGL(k_dd<true>, dim3(std::min(blocks, h->persistent_blocks)), dim3(64), dd_lds(n, h->nforest > 0), h->stream, a);
-    else
-      hipLaunchKernelGGL(k_dd<false>, dim3(std::min(blocks, h->persistent_blocks)), dim3(64), dd_lds(n, h->nforest > 0), h->stream, a);
-  } else {
-    HIPCHK(launch_cent(n, B, h->stream, a));
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->e1, h->stream));
+// The DD kernels of a step: the quasi-Newton matrix (k_dd_setup<n>: [H | I] in registers to n = DD_REG_NMAX, <0>: in
+// LDS, beyond the default 64 KB of dynamic LDS from n = 11 on), the sort by the previous step's iterations, the drain
+int launch_dd(const dat_handle* h, const KArgs& a, hipStream_t st, hipEvent_t ek) {
+  using K = void (*)(KArgs);
+  static const K reg[] = {k_dd_setup<3>, k_dd_setup<4>, k_dd_setup<5>, k_dd_setup<6>, k_dd_setup<7>, k_dd_setup<8>};
+  static_assert(DD_REG_NMAX == 8, "k_dd_setup<n>: one instantiation per n in [3, DD_REG_NMAX]");
+  const int n = a.n, B = a.B;
+  if (n > DD_REG_NMAX)
+    HIPCHK(hipFuncSetAttribute((const void*)k_dd_setup<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)dd_setup_lds(n)));
+  hipLaunchKernelGGL(n <= DD_REG_NMAX ? reg[n - 3] : k_dd_setup<0>, dim3(B), dim3(64), dd_setup_lds(n), st, a);
+  hipLaunchKernelGGL(k_dd_key, dim3((B + 63) / 64), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, st, B, (const int*)a.need, a.slist, a.scount);
+  HIPCHK(hipEventRecord(ek, st));
+  const bool env = h->nforest > 0;
+  const int G = 64 / n, blocks = std::min((B + G - 1) / G, h->persistent_blocks);
+  hipLaunchKernelGGL(env ? k_dd<true> : k_dd<false>, dim3(blocks), dim3(64), dd_lds(n, env), st, a);
   return 0;
 }
 
-// kernel arguments of the C-ADMM sub-batch of scenarios [off, off + Bs) (dat_set_sub_batches): every
-// per-scenario array offset, the env-row image a disjoint block of the SoA buffer (stride Bs n), the
+// kernel arguments of the sub-batch of scenarios [off, off + Bs) (dat_set_sub_batches; the whole batch: those of
+// kargs): every per-scenario array offset, the env-row image a disjoint block of the SoA buffer (stride Bs n), the
 // class table its own; counters shared (atomics)
 template <class T>
 T* offp(T* p, size_t k) { return p ? p + k : p; }
-KArgs sub_kargs(dat_handle* h, int off, int Bs, int s) {
+KArgs sub_kargs(const dat_handle* h, int off, int Bs, int s) {
   KArgs a = kargs(h);
   const size_t n = h->cfg.n, N3 = 3 * n, o = (size_t)off;
   a.B = Bs;
@@ -2332,22 +2330,6 @@ KArgs sub_kargs(dat_handle* h, int off, int Bs, int s) {
   return a;
 }
 
-// step_ms (optional): the device time of this step's control kernels
-int finish_hl(dat_handle* h, int ksteps = 1, double* step_ms = nullptr) {
-  HIPCHK(hipEventSynchronize(h->e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
-  h->hl_ms += ms;
-  if (step_ms) *step_ms = ms;
-  if (h->cfg.mode != DAT_MODE_CENTRALIZED) {  // k_cadmm / k_dd: from after k_bucket to the end of the step
-    float mk = 0.f;
-    HIPCHK(hipEventElapsedTime(&mk, h->ek, h->e1));
-    h->cadmm_ms += mk;
-  }
-  h->hl_steps += ksteps;
-  return 0;
-}
-
 // the open log's kernel arguments for the sub-batch of scenarios [off, ...) at the current clock
 LogArgs log_args(const dat_handle* h, int off = 0) {
   const dat_log& g = h->log;
@@ -2370,12 +2352,8 @@ LogArgs log_args(const dat_handle* h, int off = 0) {
 
 void log_free(dat_handle* h) {
   dat_log& g = h->log;
-  (void)hipFree(g.slot);
-  (void)hipFree(g.hl);
-  (void)hipFree(g.step);
-  (void)hipFree(g.sum_iters);
-  (void)hipFree(g.sum_mind);
-  (void)hipFree(g.sum_col);
+  for (void* p : {(void*)g.slot, (void*)g.hl, (void*)g.step, (void*)g.sum_iters, (void*)g.sum_mind, (void*)g.sum_col})
+    (void)hipFree(p);
   g = dat_log();
 }
 
@@ -2388,6 +2366,207 @@ int log_admit(const dat_handle* h, int hl_steps) {
     return fail("dat_closed_loop: " + std::to_string(hl_steps) + " HL steps on top of the " + std::to_string(held) +
                 " held would pass the log's hl_capacity = " + std::to_string(g.hl_cap) +
                 " (read the log and dat_log_clear, or open it larger); nothing was run");
+  return 0;
+}
+
+// ---- the step chain ------------------------------------------------------------------------------------------
+// A control step is desired acceleration -> env rows and class keys -> class sort -> drain, and in the closed loop
+// the rollout; each piece is stated once below, for one sub-batch.  dat_control_step, dat_control_steps and
+// dat_closed_loop compose them.
+
+// One sub-batch of a step: the scenarios [off, off + a.B) on their stream, and the event pair around their drain
+// (ek after the sort, e1 after the control kernels).  The whole batch is the one sub-batch of S = 1.
+struct Sub {
+  hipStream_t st;
+  KArgs a;
+  int off;
+  hipEvent_t ek, e1;
+};
+Sub sub_batch(const dat_handle* h, int s = 0, int S = 1) {
+  const long long B = h->cfg.batch;
+  Sub u;
+  u.st = h->sub[s].st;
+  u.off = (int)(B * s / S);
+  u.a = sub_kargs(h, u.off, (int)(B * (s + 1) / S) - u.off, s);
+  u.ek = h->ek;
+  u.e1 = h->e1;
+  return u;
+}
+
+// What every entry point that runs control steps starts with.  The tail stream is made here, on first use.
+int step_entry(dat_handle* h) {
+  if (!h->have_params) return fail("dat_set_params has not been called");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (tail_wanted(h)) (void)side_get(h, &h->tail, 2);
+  return 0;
+}
+
+// The inputs of a step for the scenarios of the pass `mode` (ADV_*, which picks the instantiations here): the
+// desired acceleration, then (C-ADMM) the env rows and class keys.
+enum { IN_DESIRED = 1, IN_ENV = 2 };
+void launch_inputs(const dat_handle* h, const Sub& u, int mode = ADV_ALL, int parts = IN_DESIRED | IN_ENV) {
+  struct Kernels {
+    void (*desired)(KArgs, double*);
+    void (*env_class)(KArgs);
+  };
+  static const Kernels ks[] = {{k_desired<ADV_ALL>, k_env_class<ADV_ALL>},
+                               {k_desired<ADV_EARLY>, k_env_class<ADV_EARLY>},
+                               {k_desired<ADV_REST>, k_env_class<ADV_REST>}};
+  static_assert(ADV_ALL == 0 && ADV_EARLY == 1 && ADV_REST == 2, "ks is indexed by the mode");
+  const int B = u.a.B, G = 64 / u.a.n;
+  if (parts & IN_DESIRED)
+    hipLaunchKernelGGL(ks[mode].desired, dim3((B + 63) / 64), dim3(64), 0, u.st, u.a, (double*)u.a.acc);
+  if ((parts & IN_ENV) && h->cfg.mode == DAT_MODE_CADMM)
+    hipLaunchKernelGGL(ks[mode].env_class, dim3((B + G - 1) / G), dim3(64), 0, u.st, u.a);
+}
+
+// the start of a step's timed span on one stream: the NaN pad of the residual record, e0
+int step_begin(const dat_handle* h, const Sub& u) {
+  if (h->cfg.record_err && u.a.err)
+    HIPCHK(hipMemsetAsync(u.a.err, 0xff, sizeof(double) * (size_t)u.a.B * (h->cfg.max_iter + 1), u.st));
+  HIPCHK(hipEventRecord(h->e0, u.st));
+  return 0;
+}
+
+// The control kernels of the handle's mode, between the sub-batch's two events.  a.ksteps > 1 (dat_control_steps):
+// that many control steps fused into one drain, a.acc ksteps x B x 6.
+int launch_control(const dat_handle* h, const Sub& u) {
+  const KArgs& a = u.a;
+  if (h->cfg.mode == DAT_MODE_CADMM) {  // the class sort of the step's keys (k_env_class), the drain
+    hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, u.st, a.B, (const int*)a.need, a.slist, a.scount);
+    HIPCHK(hipEventRecord(u.ek, u.st));
+    if (launch_cadmm(h, a, std::min((a.B + a.G - 1) / a.G, h->persistent_blocks), u.st)) return -1;
+  } else if (h->cfg.mode == DAT_MODE_DD) {
+    if (launch_dd(h, a, u.st, u.ek)) return -1;
+  } else {
+    HIPCHK(launch_cent(a.n, a.B, u.st, a));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(u.e1, u.st));
+  return 0;
+}
+
+// a step from its desired accelerations on; timed: on one stream, with e0 in front (after k_desired)
+int launch_step(const dat_handle* h, const Sub& u, bool timed = true) {
+  if (timed && step_begin(h, u)) return -1;
+  launch_inputs(h, u, ADV_ALL, IN_ENV);
+  return launch_control(h, u);
+}
+
+// The rollout of a closed-loop step in the pass `mode`; with a log open the recording kernel, at the log's clock
+// (sub-batch streams run unsynchronised: the record index is the sub-batch's own step count).
+void launch_step_rollout(const dat_handle* h, const Sub& u, int mode = ADV_ALL) {
+  const LogArgs lg = h->log.open ? log_args(h, u.off) : LogArgs();
+  launch_rollout(u.a, u.a.B, u.st, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes, h->log.open ? &lg : nullptr,
+                 mode);
+}
+
+double now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The accounting of enqueued steps: waits for `end`; begin -> end is added to hl_ms, each of the ndrain pairs
+// (after the sort, end of the control kernels) to cadmm_ms.  span_ms (optional): begin -> end.
+int account(dat_handle* h, hipEvent_t begin, hipEvent_t end, const hipEvent_t* drain, size_t ndrain, int steps,
+            double* span_ms = nullptr) {
+  HIPCHK(hipEventSynchronize(end));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, begin, end));
+  h->hl_ms += ms;
+  if (span_ms) *span_ms = ms;
+  for (size_t j = 0; j < ndrain; ++j) {
+    float mk = 0.f;
+    HIPCHK(hipEventElapsedTime(&mk, drain[2 * j], drain[2 * j + 1]));
+    h->cadmm_ms += mk;
+  }
+  h->hl_steps += steps;
+  return 0;
+}
+// ... of the ksteps control steps of one launch_step / launch_control on one stream (centralized: no drain span)
+int account_step(dat_handle* h, const Sub& u, int ksteps = 1, double* step_ms = nullptr) {
+  const hipEvent_t drain[2] = {u.ek, u.e1};
+  return account(h, h->e0, u.e1, drain, h->cfg.mode != DAT_MODE_CENTRALIZED, ksteps, step_ms);
+}
+
+// a step's results, copied to the host arrays that are not null (on the handle's stream, not yet synchronised)
+int copy_out(dat_handle* h, double* f_des, int* iters, int* qp_status, double* min_env_dist = nullptr,
+             unsigned char* collision = nullptr, double* err_seq = nullptr) {
+  const size_t B = h->cfg.batch, n = h->cfg.n;
+  const hipStream_t st = h->stream;
+  if (f_des) HIPCHK(hipMemcpyAsync(f_des, h->fdes, sizeof(double) * B * 3 * n, hipMemcpyDeviceToHost, st));
+  if (iters) HIPCHK(hipMemcpyAsync(iters, h->iters, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  if (qp_status) HIPCHK(hipMemcpyAsync(qp_status, h->qstatus, sizeof(int) * B * n, hipMemcpyDeviceToHost, st));
+  if (min_env_dist) HIPCHK(hipMemcpyAsync(min_env_dist, h->mind, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+  if (collision) HIPCHK(hipMemcpyAsync(collision, h->col, B, hipMemcpyDeviceToHost, st));
+  if (err_seq) {
+    if (!h->err) return fail("dat_control_step: err_seq requested but record_err = 0");
+    HIPCHK(hipMemcpyAsync(err_seq, h->err, sizeof(double) * B * (h->cfg.max_iter + 1), hipMemcpyDeviceToHost, st));
+  }
+  return 0;
+}
+
+// Does dat_closed_loop run the advance overlap?  C-ADMM on one sub-batch with no log open, the switch on, and the
+// advance stream, its event and the host word in place (three streams with the tail's, within the four hardware
+// queues).  Otherwise the serial schedule, same results.
+bool advance_ready(dat_handle* h) {
+  if (!h->adv_on || h->cfg.mode != DAT_MODE_CADMM || h->nsub != 1 || h->log.open) return false;
+  if (!h->qempty || !h->qempty_dev || !h->done || !h->adv || !h->advcnt) return false;
+  return side_get(h, &h->advance, 1) == hipSuccess;
+}
+
+// The overlap's host wait, after the drain of the step `serial` was enqueued: until the queue-empty word carries
+// the serial, at the latest until the drain has ended (dat_debug_advance_split: always until then, so that every
+// scenario's stamp is in place and the mask alone decides the split).
+int wait_queue_empty(const dat_handle* h, int serial) {
+  const volatile int* const qe = h->qempty;
+  for (;;) {
+    bool hit = false;
+    for (int k = 0; k < 256 && !hit; ++k) hit = !h->advmask && *qe == serial;
+    if (hit) break;
+    const hipError_t q = hipEventQuery(h->e1);
+    if (q == hipSuccess) break;
+    if (q != hipErrorNotReady) HIPCHK(q);
+  }
+  (void)hipGetLastError();  // (a not-ready query is no error of the loop's)
+  return 0;
+}
+
+// ---- the smaller shared pieces -------------------------------------------------------------------------------
+// Temporary device buffers of one call, freed when the scope ends, on every path (hipFree waits for the device).
+struct Scratch {
+  std::vector<void*> held;
+  Scratch() = default;
+  Scratch(const Scratch&) = delete;
+  ~Scratch() {
+    for (void* p : held) (void)hipFree(p);
+  }
+  template <class T>
+  T* get(size_t count) {  // (null when the allocation fails)
+    void* p = nullptr;
+    if (hipMalloc(&p, count ? count * sizeof(T) : 8) != hipSuccess) return nullptr;
+    held.push_back(p);
+    return (T*)p;
+  }
+};
+
+// count words from src (the handle's counters; null: zeros), read after everything enqueued on the handle's stream
+int read_words(dat_handle* h, const unsigned long long* src, unsigned long long* out, int count) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  std::fill(out, out + count, 0ull);
+  if (!src) return 0;
+  HIPCHK(hipMemcpyAsync(out, src, sizeof(*out) * count, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// ... each word to its destination, where that is not null
+int read_words(dat_handle* h, const unsigned long long* src, std::initializer_list<long long*> out) {
+  unsigned long long c[8];
+  if (read_words(h, src, c, (int)out.size())) return -1;
+  int k = 0;
+  for (long long* p : out) {
+    if (p) *p = (long long)c[k];
+    ++k;
+  }
   return 0;
 }
 
@@ -2468,12 +2647,16 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
   h->cfg = c;
   h->P = DAT_PARAM_SIZE(c.n);
   h->S = DAT_STATE_SIZE(c.n);
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&h->e0) != hipSuccess || hipEventCreate(&h->e1) != hipSuccess ||
-      hipEventCreate(&h->ek) != hipSuccess) {
-    delete h;
+  // (the side streams are made on first use, side_get)
+  hipError_t ce = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (ce == hipSuccess) h->streams.push_back(h->stream);
+  for (hipEvent_t* e : {&h->e0, &h->e1, &h->ek})
+    if (ce == hipSuccess) ce = own_event(h, e);
+  if (ce != hipSuccess) {
+    dat_destroy(h);
     return fail("dat_create: stream/event creation failed");
   }
+  h->sub[0].st = h->stream;
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.device) == hipSuccess && ncu > 0)
     h->persistent_blocks = 4 * ncu;  // k_cadmm: one wavefront per SIMD (register-bound), 4 SIMDs per CU
@@ -2571,35 +2754,13 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
 int dat_destroy(dat_handle* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->cfg.device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (hipStream_t s : h->streams) (void)hipStreamSynchronize(s);
   for (void* p : h->allocs)
     if (p) (void)hipFree(p);
-  if (h->acc_seq) (void)hipFree(h->acc_seq);
   log_free(h);
-  for (int s = 1; s < DAT_MAX_SUB; ++s) {
-    if (h->sub_stream[s]) (void)hipStreamDestroy(h->sub_stream[s]);
-    if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
-  }
-  if (h->tail_stream) {
-    (void)hipStreamSynchronize(h->tail_stream);
-    (void)hipStreamDestroy(h->tail_stream);
-  }
-  for (int e = 0; e < 2; ++e)
-    if (h->tail_ev[e]) (void)hipEventDestroy(h->tail_ev[e]);
-  if (h->adv_stream) {
-    (void)hipStreamSynchronize(h->adv_stream);
-    (void)hipStreamDestroy(h->adv_stream);
-  }
-  if (h->adv_ev) (void)hipEventDestroy(h->adv_ev);
-  if (h->advmask) (void)hipFree(h->advmask);
   if (h->qempty) (void)hipHostFree(h->qempty);
-  if (h->ev_start) (void)hipEventDestroy(h->ev_start);
-  if (h->ev_end) (void)hipEventDestroy(h->ev_end);
-  for (hipEvent_t e : h->sub_ev) (void)hipEventDestroy(e);
-  if (h->e0) (void)hipEventDestroy(h->e0);
-  if (h->e1) (void)hipEventDestroy(h->e1);
-  if (h->ek) (void)hipEventDestroy(h->ek);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
+  for (hipStream_t s : h->streams) (void)hipStreamDestroy(s);
   delete h;
   return 0;
 }
@@ -2732,27 +2893,19 @@ int dat_get_state(dat_handle* h, double* state, int* counters) {
 int dat_control_step(dat_handle* h, const double* state, const double* acc_des, double* f_des, int* iters,
                      int* qp_status, double* min_env_dist, unsigned char* collision, double* err_seq) {
   if (!h) return fail("null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const size_t B = h->cfg.batch, n = h->cfg.n;
+  if (step_entry(h)) return -1;
+  const size_t B = h->cfg.batch;
   if (state) HIPCHK(hipMemcpyAsync(h->state, state, sizeof(double) * B * h->S, hipMemcpyHostToDevice, h->stream));
-  KArgs a = kargs(h);
+  const Sub u = sub_batch(h);
   if (acc_des) {
     HIPCHK(hipMemcpyAsync(h->acc, acc_des, sizeof(double) * B * 6, hipMemcpyHostToDevice, h->stream));
   } else {
-    hipLaunchKernelGGL(k_desired<ADV_ALL>, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
+    launch_inputs(h, u, ADV_ALL, IN_DESIRED);
     HIPCHK(hipGetLastError());
   }
-  if (launch_hl(h)) return -1;
-  if (f_des) HIPCHK(hipMemcpyAsync(f_des, h->fdes, sizeof(double) * B * 3 * n, hipMemcpyDeviceToHost, h->stream));
-  if (iters) HIPCHK(hipMemcpyAsync(iters, h->iters, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-  if (qp_status) HIPCHK(hipMemcpyAsync(qp_status, h->qstatus, sizeof(int) * B * n, hipMemcpyDeviceToHost, h->stream));
-  if (min_env_dist) HIPCHK(hipMemcpyAsync(min_env_dist, h->mind, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-  if (collision) HIPCHK(hipMemcpyAsync(collision, h->col, B, hipMemcpyDeviceToHost, h->stream));
-  if (err_seq) {
-    if (!h->err) return fail("dat_control_step: err_seq requested but record_err = 0");
-    HIPCHK(hipMemcpyAsync(err_seq, h->err, sizeof(double) * B * (h->cfg.max_iter + 1), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (finish_hl(h)) return -1;
+  if (launch_step(h, u)) return -1;
+  if (copy_out(h, f_des, iters, qp_status, min_env_dist, collision, err_seq)) return -1;
+  if (account_step(h, u)) return -1;
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -2764,21 +2917,21 @@ int dat_control_steps(dat_handle* h, int steps, const double* acc_seq, double* f
     return fail("dat_control_steps: C-ADMM and DD handles only");
   if (h->nforest > 0) return fail("dat_control_steps: handles without a forest only (env rows change with the state)");
   if (h->cfg.record_err) return fail("dat_control_steps: record_err must be 0");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const size_t B = h->cfg.batch, n = h->cfg.n, need = (size_t)steps * B * 6;
+  if (step_entry(h)) return -1;
+  const size_t need = (size_t)steps * h->cfg.batch * 6;
   if (need > h->acc_seq_cap) {
-    if (h->acc_seq) HIPCHK(hipFree(h->acc_seq));
-    h->acc_seq = nullptr;
+    dfree(h, h->acc_seq);
     h->acc_seq_cap = 0;
-    HIPCHK(hipMalloc(&h->acc_seq, sizeof(double) * need));
+    if (dalloc(h, &h->acc_seq, need)) return -1;
     h->acc_seq_cap = need;
   }
   HIPCHK(hipMemcpyAsync(h->acc_seq, acc_seq, sizeof(double) * need, hipMemcpyHostToDevice, h->stream));
-  if (launch_hl(h, steps, h->acc_seq)) return -1;
-  if (f_des) HIPCHK(hipMemcpyAsync(f_des, h->fdes, sizeof(double) * B * 3 * n, hipMemcpyDeviceToHost, h->stream));
-  if (iters) HIPCHK(hipMemcpyAsync(iters, h->iters, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-  if (qp_status) HIPCHK(hipMemcpyAsync(qp_status, h->qstatus, sizeof(int) * B * n, hipMemcpyDeviceToHost, h->stream));
-  if (finish_hl(h, steps)) return -1;
+  Sub u = sub_batch(h);
+  u.a.ksteps = steps;
+  u.a.acc = h->acc_seq;
+  if (launch_step(h, u)) return -1;
+  if (copy_out(h, f_des, iters, qp_status)) return -1;
+  if (account_step(h, u, steps)) return -1;
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -2797,210 +2950,96 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
   return 0;
 }
 
-// the closed loop on sub-batches: hl_steps x (desired acceleration, env classes, class sort, C-ADMM drain,
-// rollout) per sub-batch on its own stream, no synchronisation between the sub-batches or the steps
-int closed_loop_sub(dat_handle* h, int hl_steps) {
-  if (!h->have_params) return fail("dat_set_params has not been called");
-  const int B = h->cfg.batch, n = h->cfg.n, S = h->nsub;
-  auto now_ms = [] {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  h->marks.clear();
-  h->marks.push_back(now_ms());
-  // k_cadmm launch spans: a start / end event pair per sub-batch and step, on the sub-batch's stream
-  while (h->sub_ev.size() < 2 * (size_t)S * hl_steps) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    h->sub_ev.push_back(e);
-  }
-  HIPCHK(hipEventRecord(h->ev_start, h->stream));
-  for (int s = 1; s < S; ++s) HIPCHK(hipStreamWaitEvent(h->sub_stream[s], h->ev_start, 0));
-  for (int k = 0; k < hl_steps; ++k) {
-    for (int s = 0; s < S; ++s) {
-      const int off = (int)((long long)B * s / S), Bs = (int)((long long)B * (s + 1) / S) - off;
-      hipStream_t st = h->sub_stream[s];
-      KArgs a = sub_kargs(h, off, Bs, s);
-      hipLaunchKernelGGL(k_desired<ADV_ALL>, dim3((Bs + 63) / 64), dim3(64), 0, st, a, (double*)a.acc);
-      const int G = 64 / n;
-      hipLaunchKernelGGL(k_env_class<ADV_ALL>, dim3((Bs + G - 1) / G), dim3(64), 0, st, a);
-      hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, st, Bs, (const int*)a.need, a.slist, a.scount);
-      const hipEvent_t* ev = h->sub_ev.data() + 2 * ((size_t)k * S + s);
-      HIPCHK(hipEventRecord(ev[0], st));
-      if (launch_cadmm(h, a, std::min((Bs + a.G - 1) / a.G, h->persistent_blocks), st)) return -1;
-      HIPCHK(hipEventRecord(ev[1], st));
-      if (h->log.open) {  // the streams run unsynchronised: the record index is this sub-batch's own step count
-        const LogArgs lg = log_args(h, off);
-        launch_rollout(a, Bs, st, h->cfg.hl_every, h->cfg.dt, (const double*)a.fdes, &lg);
-      } else {
-        launch_rollout(a, Bs, st, h->cfg.hl_every, h->cfg.dt, (const double*)a.fdes);
-      }
-      HIPCHK(hipGetLastError());
-    }
-    if (h->log.open) {
-      h->log.clock += h->cfg.hl_every;
-      h->log.hl_ms.push_back(std::nan(""));  // no per-step time is defined on overlapping streams
-    }
-  }
-  for (int s = 1; s < S; ++s) {
-    HIPCHK(hipEventRecord(h->sub_done[s], h->sub_stream[s]));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->sub_done[s], 0));
-  }
-  HIPCHK(hipEventRecord(h->ev_end, h->stream));
-  HIPCHK(hipEventSynchronize(h->ev_end));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev_start, h->ev_end));
-  // hl_ms: the whole run's device time (the sub-batches' kernels overlap); cadmm_ms: the sum of the
-  // k_cadmm launch spans (S launches per HL step: dat_get_kernel_ms / (hl_steps S) is one launch)
-  h->hl_ms += ms;
-  for (size_t j = 0; j < (size_t)S * hl_steps; ++j) {
-    float mk = 0.f;
-    HIPCHK(hipEventElapsedTime(&mk, h->sub_ev[2 * j], h->sub_ev[2 * j + 1]));
-    h->cadmm_ms += mk;
-  }
-  h->hl_steps += hl_steps;
-  h->marks.push_back(now_ms());
-  return 0;
-}
-
-// Does dat_closed_loop run the advance overlap?  C-ADMM on one sub-batch with no log open, the switch on, and the
-// advance stream, its event and the host word in place (the stream is created on first use, like the tail stream:
-// three streams with it, within the four hardware queues).  Otherwise the serial schedule, same results.
-bool advance_ready(dat_handle* h) {
-  if (!h->adv_on || h->cfg.mode != DAT_MODE_CADMM || h->nsub != 1 || h->log.open) return false;
-  if (!h->qempty || !h->qempty_dev || !h->done || !h->adv || !h->advcnt) return false;
-  if (!h->adv_stream) {
-    if (hipStreamCreateWithFlags(&h->adv_stream, hipStreamNonBlocking) != hipSuccess) {
-      h->adv_stream = nullptr;
-      (void)hipGetLastError();
-      return false;
-    }
-  }
-  if (!h->adv_ev && hipEventCreateWithFlags(&h->adv_ev, hipEventDisableTiming) != hipSuccess) {
-    h->adv_ev = nullptr;
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
-}
-
-// The closed loop with the advance overlap.  Per step the chain is the serial schedule's -- class sort, drain,
-// rollout, desired acceleration, env rows -- but the last three run in two passes over disjoint scenarios: `early`
-// on the advance stream beside the drain's ramp-down, on the scenarios whose done stamp is the step's, started when
-// k_cadmm's class-0 queue has been claimed empty (the host word) or the drain has ended; `rest` on the handle's
-// stream after the drain, on the others.  A scenario's step is the same sequence of the same device functions on
-// the same inputs in either pass.  The desired acceleration and env rows of a call's first step are computed for
-// every scenario up front, and none are computed after its last step (the next call starts from the state alone,
-// which dat_set_state may replace).
+// The closed loop: hl_steps x (desired acceleration, env rows and keys, control kernels, rollout), in one of three
+// schedules of the same step chain.
+//   serial       one sub-batch on the handle's stream; the host waits for each step's control kernels (the rollout
+//                still runs while the next step is enqueued).
+//   sub-batches  S of them, each on its own stream, no synchronisation between the sub-batches or the steps; the
+//                host waits once, for the call's end.
+//   overlap      (advance_ready) the serial chain with the rollout and the next step's inputs split into two passes
+//                over disjoint scenarios: `early` on the advance stream beside the drain's ramp-down, on the
+//                scenarios whose done stamp is the step's, started when k_cadmm's class-0 queue has been claimed
+//                empty (the host word) or the drain has ended; `rest` on the handle's stream after the drain, on the
+//                others.  A scenario's step is the same sequence of the same device functions on the same inputs in
+//                either pass.  The inputs of a call's first step are computed for every scenario up front, and none
+//                after its last step (the next call starts from the state alone, which dat_set_state may replace).
 // What the early pass may touch while the drain runs: a finished scenario's state, acc, env rows / mask, sort key
 // and rotation counter are read by the drain only when a slot takes the scenario (the refill; ksteps == 1 here),
 // so they may be overwritten; its f_des, iters and ipmx were stored write-through before the stamp and are read
 // past the caches; everything else the early kernels read dates from before the drain's launch.
-int closed_loop_overlap(dat_handle* h, int hl_steps) {
-  const int B = h->cfg.batch, n = h->cfg.n;
-  if (!h->have_params) return fail("dat_set_params has not been called");
-  KArgs a = kargs(h);
-  a.done = h->done;
-  a.adv = h->adv;
-  a.qempty = h->qempty_dev;
-  a.advmask = h->advmask;
-  a.advcnt = h->advcnt;
-  auto now_ms = [] {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  const int Ge = 64 / n;
-  const dim3 gd((B + 63) / 64), ge((B + Ge - 1) / Ge);
-  // the passes' kernels after the drain of step s: rollout, then (not after the call's last step) the next step's
-  // desired acceleration and env rows
-  auto advance = [&](hipStream_t st, int mode, bool next) {
-    launch_rollout(a, B, st, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes, nullptr, mode);
-    if (!next) return;
-    if (mode == ADV_EARLY) {
-      hipLaunchKernelGGL(k_desired<ADV_EARLY>, gd, dim3(64), 0, st, a, h->acc);
-      hipLaunchKernelGGL(k_env_class<ADV_EARLY>, ge, dim3(64), 0, st, a);
-    } else {
-      hipLaunchKernelGGL(k_desired<ADV_REST>, gd, dim3(64), 0, st, a, h->acc);
-      hipLaunchKernelGGL(k_env_class<ADV_REST>, ge, dim3(64), 0, st, a);
-    }
-  };
-  h->marks.clear();
-  h->marks.push_back(now_ms());
-  for (int s = 0; s < hl_steps; ++s) {
-    if (h->cfg.record_err && h->err)
-      HIPCHK(hipMemsetAsync(h->err, 0xff, sizeof(double) * (size_t)B * (h->cfg.max_iter + 1), h->stream));  // NaN pad
-    HIPCHK(hipEventRecord(h->e0, h->stream));
-    if (s == 0) {
-      hipLaunchKernelGGL(k_desired<ADV_ALL>, gd, dim3(64), 0, h->stream, a, h->acc);
-      hipLaunchKernelGGL(k_env_class<ADV_ALL>, ge, dim3(64), 0, h->stream, a);
-    }
-    h->serial = h->serial == INT_MAX ? 1 : h->serial + 1;  // (0: the arrays' initial value, no step's stamp)
-    a.serial = h->serial;
-    if (launch_sort_drain(h, a)) return -1;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->e1, h->stream));
-    // host only: until the queue-empty word carries the step's serial, at the latest until the drain has ended
-    // (dat_debug_advance_split: always until then, so that every scenario's stamp is in place and the mask alone
-    // decides the split)
-    const volatile int* const qe = h->qempty;
-    for (;;) {
-      bool hit = false;
-      for (int k = 0; k < 256 && !hit; ++k) hit = !h->advmask && *qe == a.serial;
-      if (hit) break;
-      const hipError_t q = hipEventQuery(h->e1);
-      if (q == hipSuccess) break;
-      if (q != hipErrorNotReady) HIPCHK(q);
-    }
-    (void)hipGetLastError();  // (a not-ready query is no error of the loop's)
-    const bool next = s + 1 < hl_steps;
-    advance(h->adv_stream, ADV_EARLY, next);
-    HIPCHK(hipEventRecord(h->adv_ev, h->adv_stream));
-    // (enqueued before the wait for the drain, so that its end finds them in the queue)
-    HIPCHK(hipStreamWaitEvent(h->stream, h->adv_ev, 0));
-    advance(h->stream, ADV_REST, next);
-    HIPCHK(hipGetLastError());
-    if (finish_hl(h)) return -1;
-    h->marks.push_back(now_ms());
-  }
-  return 0;
-}
-
+// With sub-batches hl_ms is the whole call's device time (the sub-batches' kernels overlap) and cadmm_ms the sum of
+// the k_cadmm launch spans (S launches per HL step: dat_get_kernel_ms / (hl_steps S) is one launch).
 int dat_closed_loop(dat_handle* h, int hl_steps) {
   if (!h) return fail("null handle");
-  if (log_admit(h, hl_steps)) return -1;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->nsub > 1) {
-    if (closed_loop_sub(h, hl_steps)) return -1;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+  if (log_admit(h, hl_steps) || step_entry(h)) return -1;
+  const int S = h->nsub;
+  const bool overlap = advance_ready(h);
+  const size_t ndrain = S > 1 && hl_steps > 0 ? (size_t)S * hl_steps : 0;
+  Sub u[DAT_MAX_SUB];
+  for (int s = 0; s < S; ++s) u[s] = sub_batch(h, s, S);
+  if (overlap) {
+    KArgs& a = u[0].a;
+    a.done = h->done;
+    a.adv = h->adv;
+    a.qempty = h->qempty_dev;
+    a.advmask = h->advmask;
+    a.advcnt = h->advcnt;
   }
-  if (advance_ready(h)) {
-    if (closed_loop_overlap(h, hl_steps)) return -1;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  const size_t B = h->cfg.batch;
-  KArgs a = kargs(h);
-  auto now_ms = [] {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  h->marks.clear();
-  h->marks.push_back(now_ms());
-  for (int s = 0; s < hl_steps; ++s) {
-    hipLaunchKernelGGL(k_desired<ADV_ALL>, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, h->acc);
-    if (launch_hl(h)) return -1;
-    if (h->log.open) {
-      const LogArgs lg = log_args(h);
-      launch_rollout(a, (int)B, h->stream, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes, &lg);
-    } else {
-      launch_rollout(a, (int)B, h->stream, h->cfg.hl_every, h->cfg.dt, (const double*)h->fdes);
+  h->marks.assign(1, now_ms());
+  if (S > 1) {  // a drain event pair per step and sub-batch; the sub-batch streams start after the handle's
+    while (h->sub_ev.size() < 2 * ndrain) {
+      hipEvent_t e = nullptr;
+      HIPCHK(own_event(h, &e));
+      h->sub_ev.push_back(e);
     }
-    HIPCHK(hipGetLastError());
-    // waits for this step's control kernel; the rollout still runs while the next step is enqueued
-    double step_ms = 0.0;
-    if (finish_hl(h, 1, &step_ms)) return -1;
+    HIPCHK(hipEventRecord(h->ev_start, h->stream));
+    for (int s = 1; s < S; ++s) HIPCHK(hipStreamWaitEvent(u[s].st, h->ev_start, 0));
+  }
+  for (int k = 0; k < hl_steps; ++k) {
+    for (int s = 0; s < S; ++s) {
+      Sub& v = u[s];
+      if (S > 1) {
+        v.ek = h->sub_ev[2 * ((size_t)k * S + s)];
+        v.e1 = h->sub_ev[2 * ((size_t)k * S + s) + 1];
+      }
+      if (!overlap) {
+        launch_inputs(h, v, ADV_ALL, IN_DESIRED);
+        if (launch_step(h, v, S == 1)) return -1;
+        launch_step_rollout(h, v);
+      } else {
+        if (step_begin(h, v)) return -1;
+        if (k == 0) launch_inputs(h, v);
+        h->serial = h->serial == INT_MAX ? 1 : h->serial + 1;  // (0: the arrays' initial value, no step's stamp)
+        v.a.serial = h->serial;
+        if (launch_control(h, v) || wait_queue_empty(h, h->serial)) return -1;
+        // the passes after the drain: the rollout, then (not after the call's last step) the next step's inputs
+        Sub early = v;
+        early.st = h->advance.st;
+        launch_step_rollout(h, early, ADV_EARLY);
+        if (k + 1 < hl_steps) launch_inputs(h, early, ADV_EARLY);
+        HIPCHK(hipEventRecord(h->advance.ev[0], early.st));
+        // (the rest pass is enqueued before the wait for the drain, so that its end finds it in the queue)
+        HIPCHK(hipStreamWaitEvent(v.st, h->advance.ev[0], 0));
+        launch_step_rollout(h, v, ADV_REST);
+        if (k + 1 < hl_steps) launch_inputs(h, v, ADV_REST);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    double step_ms = std::nan("");  // no per-step time is defined on overlapping streams
+    if (S == 1 && account_step(h, u[0], 1, &step_ms)) return -1;
     if (h->log.open) {
       h->log.clock += h->cfg.hl_every;
       h->log.hl_ms.push_back(step_ms);
     }
+    if (S == 1) h->marks.push_back(now_ms());
+  }
+  if (S > 1) {
+    for (int s = 1; s < S; ++s) {
+      HIPCHK(hipEventRecord(h->sub[s].ev[0], u[s].st));
+      HIPCHK(hipStreamWaitEvent(h->stream, h->sub[s].ev[0], 0));
+    }
+    HIPCHK(hipEventRecord(h->ev_end, h->stream));
+    if (account(h, h->ev_start, h->ev_end, h->sub_ev.data(), ndrain, hl_steps)) return -1;
     h->marks.push_back(now_ms());
   }
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -3009,13 +3048,7 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
 
 int dat_get_refinement_counters(dat_handle* h, long long* passes, long long* corrections) {
   if (!h) return fail("null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(c, h->counters + CNT_REF, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (passes) *passes = (long long)c[0];
-  if (corrections) *corrections = (long long)c[1];
-  return 0;
+  return read_words(h, h->counters + CNT_REF, {passes, corrections});
 }
 
 int dat_get_step_marks(dat_handle* h, double* marks_ms, int max_marks) {
@@ -3029,10 +3062,8 @@ int dat_get_step_marks(dat_handle* h, double* marks_ms, int max_marks) {
 int dat_get_counters(dat_handle* h, long long* qp_solves, long long* ipm_iters, long long* ipm_row_iters,
                      long long* hl_steps, double* hl_kernel_ms) {
   if (!h) return fail("null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long cc[DAT_NCOUNTERS] = {};
-  HIPCHK(hipMemcpyAsync(cc, h->counters, sizeof(cc), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  unsigned long long cc[DAT_NCOUNTERS];
+  if (read_words(h, h->counters, cc, DAT_NCOUNTERS)) return -1;
   unsigned long long c[3] = {cc[0], cc[1], cc[2]};
   if (h->cfg.mode == DAT_MODE_CADMM)
     for (int k = 1; k < NCLS; ++k)
@@ -3050,28 +3081,15 @@ int dat_get_class_counters(dat_handle* h, int env_class, long long* qp_solves, l
   if (!h) return fail("null handle");
   if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_get_class_counters: C-ADMM handles only");
   if (env_class < 0 || env_class >= NCLS) return fail("dat_get_class_counters: env_class must be in [0, 4)");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[3] = {0, 0, 0};
-  HIPCHK(hipMemcpyAsync(c, h->counters + CNT_STRIDE * env_class, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (qp_solves) *qp_solves = (long long)c[0];
-  if (ipm_iters) *ipm_iters = (long long)c[1];
-  if (ipm_row_iters) *ipm_row_iters = (long long)c[2];
   if (kernel_ms) *kernel_ms = h->cadmm_ms;
-  return 0;
+  return read_words(h, h->counters + CNT_STRIDE * env_class, {qp_solves, ipm_iters, ipm_row_iters});
 }
 
 int dat_get_class_occupancy(dat_handle* h, int env_class, long long* slot_ipm_iters, long long* wave_admm_iters) {
   if (!h) return fail("null handle");
   if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_get_class_occupancy: C-ADMM handles only");
   if (env_class < 0 || env_class >= NCLS) return fail("dat_get_class_occupancy: env_class must be in [0, 4)");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(c, h->counters + CNT_STRIDE * env_class + 3, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (slot_ipm_iters) *slot_ipm_iters = (long long)c[0];
-  if (wave_admm_iters) *wave_admm_iters = (long long)c[1];
-  return 0;
+  return read_words(h, h->counters + CNT_STRIDE * env_class + 3, {slot_ipm_iters, wave_admm_iters});
 }
 
 int dat_reset_counters(dat_handle* h) {
@@ -3097,13 +3115,11 @@ int dat_set_sub_batches(dat_handle* h, int count) {
   if (count > h->cfg.batch) return fail("dat_set_sub_batches: more sub-batches than scenarios");
   if (count > 1 && h->cfg.record_err) return fail("dat_set_sub_batches: record_err must be 0");
   HIPCHK(hipSetDevice(h->cfg.device));
-  h->sub_stream[0] = h->stream;
-  for (int s = 1; s < count; ++s) {
-    if (!h->sub_stream[s]) HIPCHK(hipStreamCreateWithFlags(&h->sub_stream[s], hipStreamNonBlocking));
-    if (!h->sub_done[s]) HIPCHK(hipEventCreateWithFlags(&h->sub_done[s], hipEventDisableTiming));
+  for (int s = 1; s < count; ++s) HIPCHK(side_get(h, &h->sub[s], 1));
+  if (count > 1) {
+    HIPCHK(own_event(h, &h->ev_start));
+    HIPCHK(own_event(h, &h->ev_end));
   }
-  if (!h->ev_start) HIPCHK(hipEventCreate(&h->ev_start));
-  if (!h->ev_end) HIPCHK(hipEventCreate(&h->ev_end));
   h->nsub = count;
   return 0;
 }
@@ -3116,15 +3132,7 @@ int dat_set_advance_overlap(dat_handle* h, int on) {
 
 int dat_get_advance_counts(dat_handle* h, long long* early, long long* late) {
   if (!h) return fail("null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[2] = {0, 0};
-  if (h->advcnt) {
-    HIPCHK(hipMemcpyAsync(c, h->advcnt, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  if (early) *early = (long long)c[0];
-  if (late) *late = (long long)c[1];
-  return 0;
+  return read_words(h, h->advcnt, {early, late});
 }
 
 int dat_debug_advance_split(dat_handle* h, const unsigned char* early_mask) {
@@ -3133,12 +3141,13 @@ int dat_debug_advance_split(dat_handle* h, const unsigned char* early_mask) {
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (!early_mask) {
-    if (h->advmask) (void)hipFree(h->advmask);
+    dfree(h, h->advmask);
     h->advmask = nullptr;
     return 0;
   }
-  if (!h->advmask) HIPCHK(hipMalloc((void**)&h->advmask, (size_t)h->cfg.batch));
-  HIPCHK(hipMemcpy(h->advmask, early_mask, (size_t)h->cfg.batch, hipMemcpyHostToDevice));
+  if (!h->advmask && dalloc(h, &h->advmask, (size_t)h->cfg.batch)) return -1;
+  HIPCHK(hipMemcpyAsync(h->advmask, early_mask, (size_t)h->cfg.batch, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -3180,29 +3189,20 @@ int dat_env_rows(dat_handle* h, double* lhs, double* rhs, int* nrow, unsigned ch
   if (!h->have_params) return fail("dat_env_rows: params not set");
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t B = h->cfg.batch, n = h->cfg.n, T = B * n;
-  double *dl, *dr, *dm;
-  int* dn;
-  unsigned char* dc;
-  HIPCHK(hipMalloc(&dl, sizeof(double) * T * DAT_NENV * 3));
-  HIPCHK(hipMalloc(&dr, sizeof(double) * T * DAT_NENV));
-  HIPCHK(hipMalloc(&dm, sizeof(double) * T));
-  HIPCHK(hipMalloc(&dn, sizeof(int) * T));
-  HIPCHK(hipMalloc(&dc, T));
+  Scratch tmp;
+  double *dl = tmp.get<double>(T * DAT_NENV * 3), *dr = tmp.get<double>(T * DAT_NENV), *dm = tmp.get<double>(T);
+  int* dn = tmp.get<int>(T);
+  unsigned char* dc = tmp.get<unsigned char>(T);
+  if (!dl || !dr || !dm || !dn || !dc) return fail("dat_env_rows: device allocation failed");
   KArgs a = kargs(h);
   hipLaunchKernelGGL(k_env, dim3((T + 63) / 64), dim3(64), 0, h->stream, a, dl, dr, dn, dc, dm);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(lhs, dl, sizeof(double) * T * DAT_NENV * 3, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rhs, dr, sizeof(double) * T * DAT_NENV, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(nrow, dn, sizeof(int) * T, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(collision, dc, T, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(min_dist, dm, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(dl);
-  (void)hipFree(dr);
-  (void)hipFree(dm);
-  (void)hipFree(dn);
-  (void)hipFree(dc);
-  if (e != hipSuccess) return fail(std::string("dat_env_rows: ") + hipGetErrorString(e));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(lhs, dl, sizeof(double) * T * DAT_NENV * 3, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(rhs, dr, sizeof(double) * T * DAT_NENV, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(nrow, dn, sizeof(int) * T, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(collision, dc, T, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(min_dist, dm, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -3233,12 +3233,11 @@ int solve_agent_qp_batch(const char* who, dat_handle* h, int count, const int* s
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t C = count, nx = dd ? 9 : N3;
-  std::vector<void*> tmp;
+  Scratch tmp;
+  bool ok = true;
   auto dev = [&](size_t bytes, const void* src) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) return nullptr;
-    tmp.push_back(p);
-    if (src && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
+    void* p = tmp.get<char>(bytes);
+    ok = ok && p && (!src || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess);
     return p;
   };
   AgentQPArgs q;
@@ -3266,32 +3265,21 @@ int solve_agent_qp_batch(const char* who, dat_handle* h, int count, const int* s
   q.mind = (double*)dev(sizeof(double) * C, nullptr);
   q.best = (double*)dev(sizeof(double) * C * best_size(1), nullptr);
   q.cert = (unsigned char*)dev(C, nullptr);
-  bool ok = q.scen && q.agent && q.acc && q.x && q.status && q.iters && q.col && q.mind && q.best && q.cert &&
-            (dd ? q.c9 != nullptr : (q.lam && q.rho && q.fbar)) && (!env_lhs || (q.elhs && q.erhs && q.nenv));
-  hipError_t e = hipSuccess;
-  if (ok) {
-    KArgs a = kargs(h);
-    e = hipEventRecord(h->e0, h->stream);
-    hipLaunchKernelGGL(k_agent_qp, dim3((count + 63) / 64), dim3(64), 0, h->stream, a, q);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(h->e1, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(x, q.x, sizeof(double) * C * nx, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(status, q.status, sizeof(int) * C, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && ipm_iters) e = hipMemcpyAsync(ipm_iters, q.iters, sizeof(int) * C, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && collision) e = hipMemcpyAsync(collision, q.col, C, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && min_env_dist)
-      e = hipMemcpyAsync(min_env_dist, q.mind, sizeof(double) * C, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && certified) e = hipMemcpyAsync(certified, q.cert, C, hipMemcpyDeviceToHost, h->stream);
-  }
-  hipError_t es = hipStreamSynchronize(h->stream);
-  if (ok && e == hipSuccess && es == hipSuccess) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->e0, h->e1) == hipSuccess) h->agent_qp_ms = ms;
-  }
-  for (void* p : tmp) (void)hipFree(p);
   if (!ok) return fail(W + "device allocation failed");
-  if (e != hipSuccess) return fail(W + hipGetErrorString(e));
-  if (es != hipSuccess) return fail(W + hipGetErrorString(es));
+  KArgs a = kargs(h);
+  HIPCHK(hipEventRecord(h->e0, h->stream));
+  hipLaunchKernelGGL(k_agent_qp, dim3((count + 63) / 64), dim3(64), 0, h->stream, a, q);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->e1, h->stream));
+  HIPCHK(hipMemcpyAsync(x, q.x, sizeof(double) * C * nx, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(status, q.status, sizeof(int) * C, hipMemcpyDeviceToHost, h->stream));
+  if (ipm_iters) HIPCHK(hipMemcpyAsync(ipm_iters, q.iters, sizeof(int) * C, hipMemcpyDeviceToHost, h->stream));
+  if (collision) HIPCHK(hipMemcpyAsync(collision, q.col, C, hipMemcpyDeviceToHost, h->stream));
+  if (min_env_dist) HIPCHK(hipMemcpyAsync(min_env_dist, q.mind, sizeof(double) * C, hipMemcpyDeviceToHost, h->stream));
+  if (certified) HIPCHK(hipMemcpyAsync(certified, q.cert, C, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, h->e0, h->e1) == hipSuccess) h->agent_qp_ms = ms;
   return 0;
 }
 }  // namespace
@@ -3326,21 +3314,15 @@ int dat_low_level_control(dat_handle* h, const double* f_des, double* thrust, do
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t B = h->cfg.batch, n = h->cfg.n;
   if (f_des) HIPCHK(hipMemcpyAsync(h->fdes, f_des, sizeof(double) * B * 3 * n, hipMemcpyHostToDevice, h->stream));
-  double *df = nullptr, *dm = nullptr;
-  HIPCHK(hipMalloc(&df, sizeof(double) * B * n));
-  if (hipMalloc(&dm, sizeof(double) * B * n * 3) != hipSuccess) {
-    (void)hipFree(df);
-    return fail("dat_low_level_control: hipMalloc failed");
-  }
+  Scratch tmp;
+  double *df = tmp.get<double>(B * n), *dm = tmp.get<double>(B * n * 3);
+  if (!df || !dm) return fail("dat_low_level_control: device allocation failed");
   KArgs a = kargs(h);
   hipLaunchKernelGGL(k_low_level, dim3((B * n + 63) / 64), dim3(64), 0, h->stream, a, (const double*)h->fdes, df, dm);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(thrust, df, sizeof(double) * B * n, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(moment, dm, sizeof(double) * B * n * 3, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(df);
-  (void)hipFree(dm);
-  if (e != hipSuccess) return fail(std::string("dat_low_level_control: ") + hipGetErrorString(e));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(thrust, df, sizeof(double) * B * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(moment, dm, sizeof(double) * B * n * 3, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -3358,30 +3340,18 @@ int dat_get_agent_qp_ms(dat_handle* h, double* ms) {
 
 int dat_get_robust_redos(dat_handle* h, long long* redos) {
   if (!h) return fail("dat_get_robust_redos: null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c = 0;
-  HIPCHK(hipMemcpyAsync(&c, h->counters + CNT_ROB, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (redos) *redos = (long long)c;
-  return 0;
+  return read_words(h, h->counters + CNT_ROB, {redos});
 }
 
 int dat_get_tail_counters(dat_handle* h, long long* out) {
   if (!h || !out) return fail("dat_get_tail_counters: null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[6] = {};
-  HIPCHK(hipMemcpyAsync(c, h->counters + CNT_TAIL, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int k = 0; k < 6; ++k) out[k] = (long long)c[k];
-  return 0;
+  return read_words(h, h->counters + CNT_TAIL, {out, out + 1, out + 2, out + 3, out + 4, out + 5});
 }
 
 int dat_get_collision_stats(dat_handle* h, long long* collisions, double* min_env_dist) {
   if (!h) return fail("dat_get_collision_stats: null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(c, h->counters + CNT_COLL, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  unsigned long long c[2];
+  if (read_words(h, h->counters + CNT_COLL, c, 2)) return -1;
   if (collisions) *collisions = (long long)c[0];
   if (min_env_dist) *min_env_dist = dist_of_key(c[1]);
   return 0;
@@ -3389,13 +3359,7 @@ int dat_get_collision_stats(dat_handle* h, long long* collisions, double* min_en
 
 int dat_get_inband_exits(dat_handle* h, long long* inband, long long* beyond_clarabel_tol) {
   if (!h) return fail("dat_get_inband_exits: null handle");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  unsigned long long c[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(c, h->counters + CNT_INBAND, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (inband) *inband = (long long)c[0];
-  if (beyond_clarabel_tol) *beyond_clarabel_tol = (long long)c[1];
-  return 0;
+  return read_words(h, h->counters + CNT_INBAND, {inband, beyond_clarabel_tol});
 }
 
 int dat_rp_rollout(dat_handle* h, int steps, const double* f) {
