@@ -156,6 +156,8 @@ EXPORTS = {
     "dat_control_steps": (ctypes.c_int, [H, ctypes.c_int, D, D, I, I]),
     "dat_set_sub_batches": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_set_advance_overlap": (ctypes.c_int, [H, ctypes.c_int]),
+    "dat_set_step_pipeline": (ctypes.c_int, [H, ctypes.c_int]),
+    "dat_get_stream_count": (ctypes.c_int, [H]),
     "dat_get_advance_counts": (ctypes.c_int, [H, LL, LL]),
     "dat_debug_advance_split": (ctypes.c_int, [H, U8]),
     "dat_get_step_marks": (ctypes.c_int, [H, D, ctypes.c_int]),

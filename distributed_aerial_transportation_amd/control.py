@@ -216,6 +216,17 @@ class BatchedController:
         """dat_set_advance_overlap: the closed loop's early advance of finished scenarios beside the drain."""
         L.check(self._lib.dat_set_advance_overlap(self._h, int(bool(on))))
 
+    def set_step_pipeline(self, on: bool) -> None:
+        """dat_set_step_pipeline: the next step's drain of the advanced scenarios starts beside the ramp-down."""
+        L.check(self._lib.dat_set_step_pipeline(self._h, int(bool(on))))
+
+    def stream_count(self) -> int:
+        """dat_get_stream_count: streams the handle holds at the moment."""
+        m = self._lib.dat_get_stream_count(self._h)
+        if m < 0:
+            L.check(m)
+        return m
+
     def advance_counts(self) -> Tuple[int, int]:
         """Scenario-steps advanced by the (early, late) pass of the advance overlap since the last reset."""
         e, l = ctypes.c_longlong(), ctypes.c_longlong()

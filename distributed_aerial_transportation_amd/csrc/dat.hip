@@ -521,6 +521,53 @@ __global__ __launch_bounds__(BUCKET_T) void k_bucket(int B, const int* need, int
     }
   }
 }
+// ... of the scenarios whose early-rollout mark adv[] is (ADV_EARLY) / is not (ADV_REST) `serial`: the step
+// pipeline's two drains of a step take disjoint lists.  A tail-routed scenario (key >= NKEY) goes to the ADV_REST
+// list wherever it was advanced, so that a step's routed scenarios run in one tail launch: the tail launches of the
+// two drains share a stream, and two of them holding stalled scenarios run one after the other.  need[] of a
+// scenario the early pass left out may be stale (its env rows are not computed yet) and is not read by the ADV_EARLY
+// sort.  The same sort otherwise; k_bucket itself stays the kernel it was (tools/same_kernels.py).
+template <int ADV>
+__global__ __launch_bounds__(BUCKET_T) void k_bucket_adv(int B, const int* need, int* list, int* count,
+                                                         const int* adv, int serial) {
+  static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the unfiltered sort is k_bucket");
+  const auto take = [&](int q) { return (adv[q] == serial && need[q] < NKEY) == (ADV == ADV_EARLY); };
+  __shared__ int hist[NKEY_ALL], kstart[NKEY_ALL], cursor[NKEY_ALL], tot[NKEY_ALL];
+  const int t = threadIdx.x;
+  if (t < NKEY_ALL) { hist[t] = 0; cursor[t] = 0; }
+  __syncthreads();
+  for (int q = t; q < B; q += BUCKET_T)
+    if (take(q)) atomicAdd(&hist[min(max(need[q], 0), NKEY_ALL - 1)], 1);
+  __syncthreads();
+  if (t == 0) {
+    int st = 0;
+    for (int k = 0; k < NKEY_ALL; ++k) { kstart[k] = st; tot[k] = hist[k]; st += hist[k]; }
+  }
+  __syncthreads();
+  for (int q = t; q < B; q += BUCKET_T) {
+    if (!take(q)) continue;
+    const int key = min(max(need[q], 0), NKEY_ALL - 1);
+    list[kstart[key] + atomicAdd(&cursor[key], 1)] = q;
+  }
+  if (t == 0) {
+    int st = 0;
+    for (int cl = 0; cl < NCLS; ++cl) {
+      int sz = 0;
+      for (int b = 0; b < NIB; ++b) sz += tot[cl * NIB + b];
+      count[sc_at(SC_SIZE, cl)] = sz;
+      count[sc_at(SC_START, cl)] = st;
+      count[sc_at(SC_HEAD, cl)] = 0;       // queue head of the class (k_cadmm)
+      count[sc_at(SC_HAND_SIZE, cl)] = 0;  // hand-over list of the class (k_cadmm -> k_cadmm_tail) and its head
+      count[sc_at(SC_HAND_HEAD, cl)] = 0;
+      st += sz;
+    }
+    for (int cl = 0; cl < NCLS; ++cl) {  // the tail-routed stretches (keys NKEY + class) behind them
+      count[sc_at(SC_TAIL_SIZE, cl)] = tot[NKEY + cl];
+      count[sc_at(SC_TAIL_START, cl)] = kstart[NKEY + cl];
+      count[sc_at(SC_TAIL_HEAD, cl)] = 0;
+    }
+  }
+}
 
 // Work counters of one wavefront, flushed once per class it drained.
 struct WaveCounters {
@@ -2006,6 +2053,9 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
 // handle + C-ABI
 // ================================================================================================
 constexpr int DAT_MAX_SUB = 4;  // sub-batches of the C-ADMM closed loop (dat_set_sub_batches)
+#ifndef DAT_STEP_PIPELINE_DEFAULT  // (A/B builds, tools/build_var.sh: -DDAT_STEP_PIPELINE_DEFAULT=false / true)
+#define DAT_STEP_PIPELINE_DEFAULT true
+#endif
 // The closed loop's log (dat_log_begin .. dat_log_end): device buffers filled by k_rollout_agents<true>, the log
 // clock and what dat_log_clear has dropped.  Held records: HL clock / hl_every - hl_base, step
 // ceil(clock / log_every) - step_base.
@@ -2028,7 +2078,7 @@ struct dat_log {
 // from the sub-batch streams.
 struct side_stream {
   hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {};
+  hipEvent_t ev[3] = {};
 };
 struct dat_handle {
   dat_log log;
@@ -2089,6 +2139,12 @@ struct dat_handle {
   unsigned long long* advcnt = nullptr;  // KArgs::advcnt
   unsigned char* advmask = nullptr;      // dat_debug_advance_split: device copy of the mask (null: not set)
   side_stream advance;                   // the early pass's stream; ev[0]: its end, joined into the handle's stream
+  // ... with the step pipeline (dat_set_step_pipeline): the early passes alternate between the advance stream and
+  // this one, each followed on its stream by the next step's main drain.  ev[0]: the early pass's end; ev[1] / ev[2]
+  // (on the handle's stream): after the rest chain's sort, after the rest drain.
+  bool pipe_on = DAT_STEP_PIPELINE_DEFAULT;
+  side_stream pipe;
+  int* pipe_lists = nullptr;  // slist and rlist of the two pipeline streams' drains (4 x B; the handle's stream: slist, rlist)
   double agent_qp_ms = 0.0;  // device time of the last dat_solve_agent_qp_batch launch
   int ll_kind = 0;  // LL_PD (example/rqp_example.py:113) or LL_SM
   // what the handle owns: dat_destroy frees by list
@@ -2154,6 +2210,21 @@ hipError_t side_get(dat_handle* h, side_stream* s, int nev) {
   h->events.insert(h->events.end(), t.ev, t.ev + nev);
   *s = t;
   return hipSuccess;
+}
+
+// ... given back, after its work has ended (dat_set_sub_batches: a handle keeps no more streams than the four
+// hardware queues it can count on); side_get makes it again on the next use
+void side_release(dat_handle* h, side_stream* s) {
+  if (!s->st) return;
+  (void)hipStreamSynchronize(s->st);
+  for (hipEvent_t v : s->ev) {
+    if (!v) continue;
+    h->events.erase(std::remove(h->events.begin(), h->events.end(), v), h->events.end());
+    (void)hipEventDestroy(v);
+  }
+  h->streams.erase(std::remove(h->streams.begin(), h->streams.end(), s->st), h->streams.end());
+  (void)hipStreamDestroy(s->st);
+  *s = side_stream();
 }
 
 // The concurrent tail launch needs a stream of its own beside the step's: with sub-batches (4 streams) a fifth and
@@ -2430,10 +2501,16 @@ int step_begin(const dat_handle* h, const Sub& u) {
 
 // The control kernels of the handle's mode, between the sub-batch's two events.  a.ksteps > 1 (dat_control_steps):
 // that many control steps fused into one drain, a.acc ksteps x B x 6.
-int launch_control(const dat_handle* h, const Sub& u) {
+// C-ADMM, the step pipeline: `mode` ADV_EARLY / ADV_REST sorts and drains only the scenarios whose mark adv[] is /
+// is not `stamp` (the previous step's serial).
+int launch_control(const dat_handle* h, const Sub& u, int mode = ADV_ALL, int stamp = 0) {
   const KArgs& a = u.a;
   if (h->cfg.mode == DAT_MODE_CADMM) {  // the class sort of the step's keys (k_env_class), the drain
-    hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, u.st, a.B, (const int*)a.need, a.slist, a.scount);
+    if (mode == ADV_ALL)
+      hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, u.st, a.B, (const int*)a.need, a.slist, a.scount);
+    else
+      hipLaunchKernelGGL(mode == ADV_EARLY ? k_bucket_adv<ADV_EARLY> : k_bucket_adv<ADV_REST>, dim3(1),
+                         dim3(BUCKET_T), 0, u.st, a.B, (const int*)a.need, a.slist, a.scount, (const int*)a.adv, stamp);
     HIPCHK(hipEventRecord(u.ek, u.st));
     if (launch_cadmm(h, a, std::min((a.B + a.G - 1) / a.G, h->persistent_blocks), u.st)) return -1;
   } else if (h->cfg.mode == DAT_MODE_DD) {
@@ -2528,6 +2605,141 @@ int wait_queue_empty(const dat_handle* h, int serial) {
     if (q != hipErrorNotReady) HIPCHK(q);
   }
   (void)hipGetLastError();  // (a not-ready query is no error of the loop's)
+  return 0;
+}
+
+// the next closed-loop step's stamp (0: the arrays' initial value, no step's stamp)
+int next_serial(dat_handle* h) { return h->serial = h->serial == INT_MAX ? 1 : h->serial + 1; }
+
+// Does dat_closed_loop run the step pipeline?  Where the advance overlap runs, with the switch on, no residual
+// record (its per-step pad is a whole-batch memset), and the second pipeline stream and the two further list sets
+// in place: four streams with the tail's.  Otherwise the overlap schedule (or the serial one), same results.
+bool pipeline_ready(dat_handle* h) {
+  if (!h->pipe_on || h->cfg.record_err || !advance_ready(h)) return false;
+  if (side_get(h, &h->pipe, 3) != hipSuccess) return false;
+  if (!h->pipe_lists && dalloc(h, &h->pipe_lists, (size_t)4 * h->cfg.batch)) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+
+// The closed loop as a step pipeline: per step two drains over disjoint scenarios.  The main drain of
+// step k + 1 takes the scenarios the early pass of step k advanced and is enqueued directly behind that pass, on
+// its stream: it starts beside step k's ramp-down and its workgroups are dispatched as the old ones retire.  The
+// rest drain of step k + 1 takes the others, on the handle's stream, after both drains of step k have ended and the
+// rest pass has advanced them.  What a drain reads of a scenario while the previous step's drains still run -- the
+// warm state, plain stores of the drain that finished it -- has been written back by the kernel boundaries between
+// the two (the early pass and the sort run after the stamp was seen); everything else it touches is the scenario's
+// own and has one writer per step.  The early passes alternate between two streams, so that the pass of step k + 1
+// does not queue behind the main drain of step k + 1.  Each of the three streams that run drains has its own
+// class table and lists (a stream's drains are ordered, so a set is rewritten only after its last reader), and
+// each step its own timed event pair.  The host never waits inside the loop: it polls the host word and queries
+// events, and reads the spans at the end of the call.
+int closed_loop_pipelined(dat_handle* h, int hl_steps) {
+  const int B = h->cfg.batch;
+  side_stream* const X[2] = {&h->advance, &h->pipe};
+  while (h->sub_ev.size() < 2 * (size_t)hl_steps) {
+    hipEvent_t e = nullptr;
+    HIPCHK(own_event(h, &e));
+    h->sub_ev.push_back(e);
+  }
+  Sub base = sub_batch(h);
+  base.a.done = h->done;
+  base.a.adv = h->adv;
+  base.a.qempty = h->qempty_dev;
+  base.a.advmask = h->advmask;
+  base.a.advcnt = h->advcnt;
+  // the main drain of step k: on the handle's stream over every scenario (k = 0, the first of the call), else on
+  // the stream of the early pass it follows
+  const auto main_drain = [&](int k, int serial) {
+    Sub m = base;
+    if (k > 0) {
+      const int j = (k - 1) & 1;
+      m.st = X[j]->st;
+      m.a.slist = h->pipe_lists + (size_t)2 * j * B;
+      m.a.rlist = m.a.slist + B;
+      m.a.scount = h->scount + SCOUNT_INTS * (1 + j);  // (one sub-batch: the other sub-batches' tables are free)
+    }
+    m.a.serial = serial;
+    m.ek = h->sub_ev[2 * (size_t)k];
+    m.e1 = h->sub_ev[2 * (size_t)k + 1];
+    return m;
+  };
+  h->marks.assign(1, now_ms());
+  int marked = 0;  // steps whose main drain the host has seen ended
+  const auto mark = [&](int upto) {
+    while (marked < upto && hipEventQuery(h->sub_ev[2 * (size_t)marked + 1]) == hipSuccess) {
+      h->marks.push_back(now_ms());
+      ++marked;
+    }
+    (void)hipGetLastError();  // (a not-ready query is no error of the loop's)
+  };
+  HIPCHK(hipEventRecord(h->e0, h->stream));
+  launch_inputs(h, base);
+  int serial = next_serial(h);
+  if (launch_control(h, main_drain(0, serial))) return -1;
+  for (int k = 0; k < hl_steps; ++k) {
+    const bool more = k + 1 < hl_steps;
+    const hipEvent_t e1 = h->sub_ev[2 * (size_t)k + 1];
+    // until the main drain's class-0 queue has been claimed empty, at the latest until the drain has ended
+    // (dat_debug_advance_split: always until then)
+    for (const volatile int* const qe = h->qempty;;) {
+      bool hit = false;
+      for (int q = 0; q < 256 && !hit; ++q) hit = !h->advmask && *qe == serial;
+      mark(k);
+      if (hit) break;
+      const hipError_t q = hipEventQuery(e1);
+      if (q == hipSuccess) break;
+      if (q != hipErrorNotReady) HIPCHK(q);
+    }
+    (void)hipGetLastError();  // (a not-ready query is no error of the loop's)
+    // the early pass of step k.  It marks adv[], which the rest chain of step k - 1 reads as its gate: after that
+    // chain's sort.  With the split forced it also follows the rest drain of step k, for every stamp to be in place.
+    side_stream& x = *X[k & 1];
+    Sub early = base;
+    early.st = x.st;
+    early.a.serial = serial;
+    if (k > 0) HIPCHK(hipStreamWaitEvent(x.st, h->pipe.ev[1], 0));
+    if (k > 0 && h->advmask) HIPCHK(hipStreamWaitEvent(x.st, h->pipe.ev[2], 0));
+    launch_step_rollout(h, early, ADV_EARLY);
+    if (more) launch_inputs(h, early, ADV_EARLY);
+    HIPCHK(hipEventRecord(x.ev[0], x.st));
+    const int next = more ? next_serial(h) : 0;
+    if (more && launch_control(h, main_drain(k + 1, next), ADV_EARLY, serial)) return -1;
+    // the rest chain of step k on the handle's stream (where the step's rest drain ran): after its main drain and
+    // the early pass, the rest pass; then the sort and the drain of what it advanced.  That drain keeps the host
+    // word out of it: its queue-empty store goes to a spare word of the class tables.
+    Sub rest = base;
+    rest.a.serial = serial;
+    if (k > 0) HIPCHK(hipStreamWaitEvent(rest.st, e1, 0));
+    HIPCHK(hipStreamWaitEvent(rest.st, x.ev[0], 0));
+    launch_step_rollout(h, rest, ADV_REST);
+    if (more) {
+      launch_inputs(h, rest, ADV_REST);
+      rest.a.serial = next;
+      rest.a.qempty = h->scount + SCOUNT_INTS * 3;
+      rest.ek = h->pipe.ev[1];
+      rest.e1 = h->pipe.ev[2];
+      if (launch_control(h, rest, ADV_REST, serial)) return -1;
+    }
+    HIPCHK(hipGetLastError());
+    serial = next;
+  }
+  // the call's end: the handle's stream has joined the last main drain and early pass, and through them the others
+  HIPCHK(hipEventRecord(h->e1, h->stream));
+  HIPCHK(hipEventSynchronize(h->e1));
+  for (side_stream* s : X) HIPCHK(hipStreamSynchronize(s->st));
+  if (h->tail.st) HIPCHK(hipStreamSynchronize(h->tail.st));
+  mark(hl_steps);
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+  h->hl_ms += ms;
+  for (int k = 0; k < hl_steps; ++k) {  // (the main drains' spans: those of consecutive steps overlap)
+    HIPCHK(hipEventElapsedTime(&ms, h->sub_ev[2 * (size_t)k], h->sub_ev[2 * (size_t)k + 1]));
+    h->cadmm_ms += ms;
+  }
+  h->hl_steps += hl_steps;
   return 0;
 }
 
@@ -2950,7 +3162,7 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
   return 0;
 }
 
-// The closed loop: hl_steps x (desired acceleration, env rows and keys, control kernels, rollout), in one of three
+// The closed loop: hl_steps x (desired acceleration, env rows and keys, control kernels, rollout), in one of four
 // schedules of the same step chain.
 //   serial       one sub-batch on the handle's stream; the host waits for each step's control kernels (the rollout
 //                still runs while the next step is enqueued).
@@ -2963,6 +3175,9 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
 //                others.  A scenario's step is the same sequence of the same device functions on the same inputs in
 //                either pass.  The inputs of a call's first step are computed for every scenario up front, and none
 //                after its last step (the next call starts from the state alone, which dat_set_state may replace).
+//   pipeline     (pipeline_ready; closed_loop_pipelined) the overlap with the next step's drain split likewise: the
+//                scenarios the early pass has advanced are sorted and drained directly behind it, beside the current
+//                drain's ramp-down, the others after the rest pass.
 // What the early pass may touch while the drain runs: a finished scenario's state, acc, env rows / mask, sort key
 // and rotation counter are read by the drain only when a slot takes the scenario (the refill; ksteps == 1 here),
 // so they may be overwritten; its f_des, iters and ipmx were stored write-through before the stamp and are read
@@ -2973,6 +3188,7 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
   if (!h) return fail("null handle");
   if (log_admit(h, hl_steps) || step_entry(h)) return -1;
   const int S = h->nsub;
+  if (hl_steps > 0 && pipeline_ready(h)) return closed_loop_pipelined(h, hl_steps);
   const bool overlap = advance_ready(h);
   const size_t ndrain = S > 1 && hl_steps > 0 ? (size_t)S * hl_steps : 0;
   Sub u[DAT_MAX_SUB];
@@ -3009,8 +3225,7 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
       } else {
         if (step_begin(h, v)) return -1;
         if (k == 0) launch_inputs(h, v);
-        h->serial = h->serial == INT_MAX ? 1 : h->serial + 1;  // (0: the arrays' initial value, no step's stamp)
-        v.a.serial = h->serial;
+        v.a.serial = next_serial(h);
         if (launch_control(h, v) || wait_queue_empty(h, h->serial)) return -1;
         // the passes after the drain: the rollout, then (not after the call's last step) the next step's inputs
         Sub early = v;
@@ -3115,6 +3330,12 @@ int dat_set_sub_batches(dat_handle* h, int count) {
   if (count > h->cfg.batch) return fail("dat_set_sub_batches: more sub-batches than scenarios");
   if (count > 1 && h->cfg.record_err) return fail("dat_set_sub_batches: record_err must be 0");
   HIPCHK(hipSetDevice(h->cfg.device));
+  // a handle keeps at most four streams: its own and the sub-batches' further ones, or (one sub-batch) its own and
+  // on first use the tail's, the advance stream and the pipeline's second
+  if (count > 1)
+    for (side_stream* s : {&h->tail, &h->advance, &h->pipe}) side_release(h, s);
+  for (int s = count; s < DAT_MAX_SUB; ++s)
+    if (s > 0) side_release(h, &h->sub[s]);
   for (int s = 1; s < count; ++s) HIPCHK(side_get(h, &h->sub[s], 1));
   if (count > 1) {
     HIPCHK(own_event(h, &h->ev_start));
@@ -3128,6 +3349,17 @@ int dat_set_advance_overlap(dat_handle* h, int on) {
   if (!h) return fail("null handle");
   h->adv_on = on != 0;
   return 0;
+}
+
+int dat_set_step_pipeline(dat_handle* h, int on) {
+  if (!h) return fail("null handle");
+  h->pipe_on = on != 0;
+  return 0;
+}
+
+int dat_get_stream_count(dat_handle* h) {
+  if (!h) return fail("null handle");
+  return (int)h->streams.size();
 }
 
 int dat_get_advance_counts(dat_handle* h, long long* early, long long* late) {

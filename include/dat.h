@@ -157,6 +157,20 @@ int dat_set_sub_batches(dat_handle* h, int count);
  * bitwise that of the serial schedule (on = 0), which sub-batches, an open log, the other modes and the
  * step-by-step entry points keep. */
 int dat_set_advance_overlap(dat_handle* h, int on);
+/* Where the advance overlap runs (and record_err = 0): the step pipeline (default on).  Each step's drain is split in
+ * two over disjoint scenarios.  The main drain of step k + 1 takes the scenarios the early pass of step k advanced
+ * and is enqueued directly behind that pass on its stream, so it starts beside step k's ramp-down; the rest drain
+ * of step k + 1 takes the others, on the handle's stream, after both drains of step k and the late pass.  The early
+ * passes alternate between two streams; with the tail's the handle then holds four.  A call's first step is one
+ * drain over all scenarios, after its last step only rollouts run, and at return every scenario is at the same
+ * step and every stream idle.  A scenario's arithmetic does not depend on the drain that runs it: every result is
+ * bitwise that of the overlap schedule (on = 0) and of the serial one.  dat_get_kernel_ms sums the main drains'
+ * spans, which overlap between consecutive steps; the step marks are taken when the host first finds a step's main
+ * drain ended. */
+int dat_set_step_pipeline(dat_handle* h, int on);
+/* Streams the handle holds at the moment (its own, and the side streams made on first use): never more than four.
+ * dat_set_sub_batches gives back the streams its new count does not use. */
+int dat_get_stream_count(dat_handle* h);
 /* Scenario-steps advanced by the early and by the late pass of the advance overlap since the last counter
  * reset; their sum is batch x HL steps run under the overlap (both 0 where the serial schedule ran). */
 int dat_get_advance_counts(dat_handle* h, long long* early, long long* late);
