@@ -237,13 +237,13 @@ __device__ inline int env_class_of(unsigned emask, const double lhs[DAT_NENV][3]
 }
 
 // Env rows of the n agents of each scenario of a 64-lane block, computed cooperatively
-// (control/rqp_cadmm.py:307-373 via env_rows' arithmetic).  The payload capsule and the x-window of
+// (control/rqp_cadmm.py:307-373 from env_rows' pieces, dat_core.hpp).  The payload capsule and the x-window of
 // candidate trees are the same for every agent of a scenario; only the camera-cone filter differs
 // (cos 100 deg: most agents see most trees).  Lane i of a scenario evaluates trees base + i of each
 // chunk of n candidates -- range test, capsule_tree distance and the CBF row, once per tree instead
 // of once per agent that sees it -- and publishes them in LDS; then every lane runs its own cone
-// filter and sorted insertion over the chunk in tree order.  Same per-tree arithmetic and insertion
-// order as env_rows (the rows are bitwise identical; test_gpu_env_rows / test_gpu_c4).
+// filter and sorted insertion over the chunk in tree order.  The pieces and the insertion order are env_rows',
+// so the rows are bitwise identical by construction (test_gpu_env_rows / test_gpu_c4 check it).
 // Must be called by every lane of the block (barriers inside).
 constexpr int ENV_CE = 8;  // published entry: in range, c.x, c.y, dd, l3[3], r1
 // LDS stride of a published entry: 9 doubles (18 dwords), so the 32 lanes of a ds_*_b64 half-wave
@@ -256,84 +256,33 @@ __device__ EnvOut env_rows_coop(const double* prm, int n, const double* st, cons
   out.collision = 0;
   out.min_env_dist = valid ? prm[DAT_P_VISR] : 0.0;
   *mask = 0u;
-#pragma unroll
-  for (int j = 0; j < DAT_NENV; ++j) { lhs[j][0] = lhs[j][1] = lhs[j][2] = 0.0; rhs[j] = 0.0; }
   const bool any = valid && trees != nullptr && ntree > 0;
   bool dead = !any;  // this agent keeps no row (it still evaluates its share of the trees)
-  double xl[3] = {0, 0, 0}, vl[3] = {0, 0, 0}, vdir[3] = {0, 0, 0}, seg[3] = {0, 0, 0}, ctr[3] = {0, 0, 0};
-  double h = 0.0, speed = 0.0, maxdec = 1.0, reach = 0.0, rc = 0.0, deps = 0.0, cosang = 0.0;
-  double cam[2] = {0, 0}, dir[2] = {0, 0};
+  EnvFrame fr;
+  EnvCam cam;
   int t0 = 0;
   if (any) {
-    const double* xlp = st + DAT_S_XL(n);
-    const double* vlp = st + DAT_S_VL(n);
-    const double* Rl = st + DAT_S_RL(n);
-    for (int c = 0; c < 3; ++c) { xl[c] = xlp[c]; vl[c] = vlp[c]; }
-    maxdec = prm[DAT_P_MAXDEC];
-    rc = prm[DAT_P_COLR];
-    deps = prm[DAT_P_DISTEPS];
-    cosang = prm[DAT_P_COSCONE];
-    const double v2 = dot3(vl, vl);
-    h = 0.5 * v2 / maxdec;
-    speed = sqrt(v2);
-    ctr[0] = xl[0]; ctr[1] = xl[1]; ctr[2] = xl[2];
-    if (speed != 0.0) {
-      vdir[0] = vl[0] / speed; vdir[1] = vl[1] / speed; vdir[2] = vl[2] / speed;
-      seg[0] = h * vdir[0]; seg[1] = h * vdir[1]; seg[2] = h * vdir[2];
-      ctr[0] += 0.5 * seg[0]; ctr[1] += 0.5 * seg[1]; ctr[2] += 0.5 * seg[2];
-    }
-    const double* r = prm + DAT_P_R(n) + 3 * i;
-    double Rr[3];
-    mv3(Rl, r, Rr);
-    cam[0] = xl[0] + Rr[0];
-    cam[1] = xl[1] + Rr[1];
-    const double dx = cam[0] - xl[0], dy = cam[1] - xl[1];
-    const double nn = sqrt(dx * dx + dy * dy);
-    if (nn == 0.0) {
+    env_frame(prm, n, st, fr);
+    if (!env_camera(prm, n, st, i, cam)) {
       out.collision = 1;
       dead = true;
-    } else {
-      dir[0] = dx / nn; dir[1] = dy / nn;
     }
-    reach = prm[DAT_P_VISR] + DAT_BARK_RADIUS;
-    for (int len = ntree; len > 0;) {
-      int half = len >> 1;
-      if (trees[3 * (t0 + half)] < ctr[0] - reach) { t0 += half + 1; len -= half + 1; } else { len = half; }
-    }
+    t0 = env_window_begin(fr, trees, ntree);
   }
-  double bd[DAT_NENV];
-#pragma unroll
-  for (int j = 0; j < DAT_NENV; ++j) bd[j] = 1e300;
-  int cnt = 0;
-  double dmin = 1e300;
+  EnvSeen seen;
+  env_clear(seen, lhs, rhs);
   double* mine = ent + (size_t)threadIdx.x * ENV_CS;
   const double* grp = ent + (size_t)(ls * n) * ENV_CS;
   for (int base = t0;; base += n) {
     // this lane's tree of the chunk
     const int t = base + i;
-    const bool cand = any && t < ntree && trees[3 * t] <= ctr[0] + reach;
+    const bool cand = any && t < ntree && trees[3 * t] <= fr.ctr[0] + fr.reach;
     double e[ENV_CE] = {0, 0, 0, 1e300, 0, 0, 0, 0};
     if (cand) {
       const double* c = trees + 3 * t;
-      const double ex = ctr[0] - c[0], ey = ctr[1] - c[1], ez = ctr[2] - c[2];
-      if (!(sqrt(ex * ex + ey * ey + ez * ez) > prm[DAT_P_VISR] + DAT_BARK_RADIUS)) {
-        double p1[3], p2[3];
-        const double dd = capsule_tree(xl, seg, rc, c, p1, p2);
-        double l3[3] = {0, 0, 0}, r1 = 0.0;
-        if (dd > 1e-4 && speed > 0.0) {
-          double rel[3] = {p1[0] - xl[0], p1[1] - xl[1], p1[2] - xl[2]};
-          double proj = fmax(0.0, fmin(h, dot3(rel, vdir)));
-          double mt = sqrt(2.0 * (h - proj) / maxdec);
-          mt = fmax(0.0, speed / maxdec - mt);
-          if (mt < 1e-12 * speed / maxdec) mt = 0.0;
-          double nr[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-          double nn = sqrt(dot3(nr, nr));
-          nr[0] /= nn; nr[1] /= nn; nr[2] /= nn;
-          l3[0] = nr[0] * mt; l3[1] = nr[1] * mt; l3[2] = nr[2] * mt;
-          r1 = -alpha_env * (dd - deps) - dot3(nr, vl);
-        }
-        e[0] = 1.0; e[1] = c[0]; e[2] = c[1]; e[3] = dd;
-        e[4] = l3[0]; e[5] = l3[1]; e[6] = l3[2]; e[7] = r1;
+      if (env_in_range(fr, c)) {
+        e[0] = 1.0; e[1] = c[0]; e[2] = c[1];
+        e[3] = env_tree_row(fr, alpha_env, c, e + 4);
       }
     }
     // every lane of the block takes part in the barriers; the loop ends when no lane had a candidate
@@ -345,44 +294,17 @@ __device__ EnvOut env_rows_coop(const double* prm, int n, const double* st, cons
       for (int j = 0; j < n; ++j) {  // the chunk in tree order
         const double* q = grp + (size_t)j * ENV_CS;
         if (q[0] == 0.0) continue;
-        const double tx = q[1] - cam[0], ty = q[2] - cam[1];
-        const double nn = sqrt(tx * tx + ty * ty);
-        if (nn > 0.0 && (tx / nn * dir[0] + ty / nn * dir[1]) < cosang) continue;
+        if (!env_in_cone(cam, q[1], q[2])) continue;
         const double dd = q[3];
-        if (dd < 1e-4) out.collision = 1;
-        dmin = fmin(dmin, dd);
-        ++cnt;
-        int pos = 0;
-#pragma unroll
-        for (int jj = 0; jj < DAT_NENV; ++jj) pos += (bd[jj] <= dd) ? 1 : 0;
-        if (pos >= DAT_NENV) continue;
-#pragma unroll
-        for (int jj = DAT_NENV - 1; jj >= 1; --jj) {
-          if (jj > pos) {
-            bd[jj] = bd[jj - 1];
-            lhs[jj][0] = lhs[jj - 1][0]; lhs[jj][1] = lhs[jj - 1][1]; lhs[jj][2] = lhs[jj - 1][2];
-            rhs[jj] = rhs[jj - 1];
-          }
-        }
-#pragma unroll
-        for (int jj = 0; jj < DAT_NENV; ++jj) {
-          if (jj == pos) {
-            bd[jj] = dd;
-            lhs[jj][0] = q[4]; lhs[jj][1] = q[5]; lhs[jj][2] = q[6];
-            rhs[jj] = q[7];
-          }
-        }
+        if (dd < ENV_TOUCH) out.collision = 1;
+        env_see(seen, dd, q + 4, lhs, rhs);
       }
     }
     __syncthreads();  // the chunk is consumed before the next one is published
   }
-  if (!dead && cnt > 0 && speed > 0.0) {
-    out.min_env_dist = dmin;
-    unsigned m = 0u;
-#pragma unroll
-    for (int j = 0; j < DAT_NENV; ++j)
-      if (bd[j] < 1e299 && bd[j] > 1e-4) m |= 1u << j;
-    *mask = m;
+  if (!dead && seen.cnt > 0 && fr.speed > 0.0) {
+    out.min_env_dist = seen.dmin;
+    *mask = env_mask(seen);
   }
   return out;
 }
@@ -485,53 +407,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 // scenarios share a wavefront, never a scenario's arithmetic (the capped-grid test compares two
 // different groupings bitwise).
 constexpr int BUCKET_T = 1024;
-static_assert(NKEY_ALL <= BUCKET_T, "k_bucket initialises one key per thread");
-__global__ __launch_bounds__(BUCKET_T) void k_bucket(int B, const int* need, int* list, int* count) {
-  __shared__ int hist[NKEY_ALL], kstart[NKEY_ALL], cursor[NKEY_ALL], tot[NKEY_ALL];
-  const int t = threadIdx.x;
-  if (t < NKEY_ALL) { hist[t] = 0; cursor[t] = 0; }
-  __syncthreads();
-  for (int q = t; q < B; q += BUCKET_T) atomicAdd(&hist[min(max(need[q], 0), NKEY_ALL - 1)], 1);
-  __syncthreads();
-  if (t == 0) {
-    int st = 0;
-    for (int k = 0; k < NKEY_ALL; ++k) { kstart[k] = st; tot[k] = hist[k]; st += hist[k]; }
-  }
-  __syncthreads();
-  for (int q = t; q < B; q += BUCKET_T) {
-    const int key = min(max(need[q], 0), NKEY_ALL - 1);
-    list[kstart[key] + atomicAdd(&cursor[key], 1)] = q;
-  }
-  if (t == 0) {
-    int st = 0;
-    for (int cl = 0; cl < NCLS; ++cl) {
-      int sz = 0;
-      for (int b = 0; b < NIB; ++b) sz += tot[cl * NIB + b];
-      count[sc_at(SC_SIZE, cl)] = sz;
-      count[sc_at(SC_START, cl)] = st;
-      count[sc_at(SC_HEAD, cl)] = 0;       // queue head of the class (k_cadmm)
-      count[sc_at(SC_HAND_SIZE, cl)] = 0;  // hand-over list of the class (k_cadmm -> k_cadmm_tail) and its head
-      count[sc_at(SC_HAND_HEAD, cl)] = 0;
-      st += sz;
-    }
-    for (int cl = 0; cl < NCLS; ++cl) {  // the tail-routed stretches (keys NKEY + class) behind them
-      count[sc_at(SC_TAIL_SIZE, cl)] = tot[NKEY + cl];
-      count[sc_at(SC_TAIL_START, cl)] = kstart[NKEY + cl];
-      count[sc_at(SC_TAIL_HEAD, cl)] = 0;
-    }
-  }
-}
-// ... of the scenarios whose early-rollout mark adv[] is (ADV_EARLY) / is not (ADV_REST) `serial`: the step
+static_assert(NKEY_ALL <= BUCKET_T, "bucket_sort initialises one key per thread");
+// ADV_EARLY / ADV_REST: ... of the scenarios whose early-rollout mark adv[] is / is not `serial`: the step
 // pipeline's two drains of a step take disjoint lists.  A tail-routed scenario (key >= NKEY) goes to the ADV_REST
 // list wherever it was advanced, so that a step's routed scenarios run in one tail launch: the tail launches of the
 // two drains share a stream, and two of them holding stalled scenarios run one after the other.  need[] of a
 // scenario the early pass left out may be stale (its env rows are not computed yet) and is not read by the ADV_EARLY
-// sort.  The same sort otherwise; k_bucket itself stays the kernel it was (tools/same_kernels.py).
+// sort.  ADV_ALL: every scenario (adv is not read).
 template <int ADV>
-__global__ __launch_bounds__(BUCKET_T) void k_bucket_adv(int B, const int* need, int* list, int* count,
-                                                         const int* adv, int serial) {
-  static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the unfiltered sort is k_bucket");
-  const auto take = [&](int q) { return (adv[q] == serial && need[q] < NKEY) == (ADV == ADV_EARLY); };
+__device__ __forceinline__ void bucket_sort(int B, const int* need, int* list, int* count, const int* adv,
+                                            int serial) {
+  const auto take = [&](int q) {
+    if constexpr (ADV == ADV_ALL) return true;
+    else return (adv[q] == serial && need[q] < NKEY) == (ADV == ADV_EARLY);
+  };
   __shared__ int hist[NKEY_ALL], kstart[NKEY_ALL], cursor[NKEY_ALL], tot[NKEY_ALL];
   const int t = threadIdx.x;
   if (t < NKEY_ALL) { hist[t] = 0; cursor[t] = 0; }
@@ -567,6 +456,15 @@ __global__ __launch_bounds__(BUCKET_T) void k_bucket_adv(int B, const int* need,
       count[sc_at(SC_TAIL_HEAD, cl)] = 0;
     }
   }
+}
+__global__ __launch_bounds__(BUCKET_T) void k_bucket(int B, const int* need, int* list, int* count) {
+  bucket_sort<ADV_ALL>(B, need, list, count, nullptr, 0);
+}
+template <int ADV>
+__global__ __launch_bounds__(BUCKET_T) void k_bucket_adv(int B, const int* need, int* list, int* count,
+                                                         const int* adv, int serial) {
+  static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the unfiltered sort is k_bucket");
+  bucket_sort<ADV>(B, need, list, count, adv, serial);
 }
 
 // Work counters of one wavefront, flushed once per class it drained.
@@ -1482,13 +1380,10 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
         // place at :725), so agent 0's fallback sums the controller's current forces (every agent's
         // f before this iteration's writes); the other agents sum their own f_eq.
         const double* feq = prm + DAT_P_FEQ(n);
-        double s3[3] = {0, 0, 0}, jr[3], rf[3];
+        double s3[3] = {0, 0, 0};
         for (int k = 0; k < n; ++k)
           for (int c = 0; c < 3; ++c) s3[c] += (i == 0) ? X[(ls * n + k) * 9 + c] : feq[3 * k + c];
-        for (int c = 0; c < 3; ++c) { prev[c] = feq[3 * i + c]; prev[3 + c] = s3[c] - feq[3 * i + c]; }
-        cross3(prm + DAT_P_RCOM(n) + 3 * i, prev, rf);
-        mv3(prm + DAT_P_JTI, rf, jr);
-        for (int c = 0; c < 3; ++c) prev[6 + c] = -jr[c];
+        dd_fallback(prm, n, i, s3, prev);
       }
     }
     DAT_PHASE(13);
@@ -1608,8 +1503,8 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
 // `steps` simulation steps (sim_step, system/rigid_quadrotor_payload.py:129-222) with one lane per (scenario, agent): G = floor(64/n) scenarios
 // per 64-lane block.  Lane i runs agent i's low-level law, rotational dynamics and attitude
 // integration; the payload's force / moment sums go through LDS and every lane of the scenario
-// integrates the payload identically (sums in agent order, the arithmetic of sim_step: bitwise the
-// same trajectory).  Per-lane state is one quadrotor plus the payload (~40 doubles), so nothing
+// integrates the payload identically (sums in agent order, the pieces of sim_step, dat_core.hpp: bitwise
+// the same trajectory by construction).  Per-lane state is one quadrotor plus the payload (~40 doubles), so nothing
 // spills and the kernel runs many wavefronts per SIMD, for any n (k_rollout<0> kept the whole state
 // of a large team in scratch).
 //
@@ -1713,7 +1608,7 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
   for (int s = 0; s < steps; ++s) {
     double dw[3] = {0, 0, 0};
     if (valid) {
-      double f, M[3], Jw[3], wJw[3], t[3];
+      double f, M[3];
       ll_control_agent(R, W, J, fd, &f, M, a.ll_kind);
       if constexpr (LOG) {
         if (s == lnext && lslot[lane] >= 0) {  // 32-byte aligned: two 16-byte stores
@@ -1722,62 +1617,22 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
           w[1] = make_double2(M[1], M[2]);
         }
       }
-      mv3(J, W, Jw);
-      cross3(W, Jw, wJw);
-      for (int c = 0; c < 3; ++c) t[c] = M[c] - wJw[c];
-      mv3(Ji, t, dw);
-      double u[3] = {R[2] * f, R[5] * f, R[8] * f};  // f R e3
-      double ub[3], m3[3];
-      mtv3(Rl, u, ub);
-      cross3(prm + DAT_P_RCOM(n) + 3 * i, ub, m3);
-      for (int c = 0; c < 3; ++c) { mine[c] = u[c]; mine[3 + c] = m3[c]; }
+      double um[RO_X];
+      quad_accel(R, W, J, Ji, prm + DAT_P_RCOM(n) + 3 * i, Rl, f, M, dw, um);
+      for (int c = 0; c < RO_X; ++c) mine[c] = um[c];
     }
     __syncthreads();
     if (valid) {
-      double dvc[3] = {0, 0, 0}, mom[3] = {0, 0, 0};
+      double dvc[3] = {0, 0, 0}, mom[3] = {0, 0, 0}, dvl[3], dwl[3];
       for (int k = 0; k < n; ++k)
         for (int c = 0; c < 3; ++c) { dvc[c] += grp[k * RO_X + c]; mom[c] += grp[k * RO_X + 3 + c]; }
-      const double mT = prm[DAT_P_MT];
-      const double* xc = prm + DAT_P_XCOM;
-      for (int c = 0; c < 3; ++c) dvc[c] /= mT;
-      dvc[2] -= DAT_GRAVITY;
-      double Jwl[3], wJwl[3], t[3], dwl[3];
-      mv3(prm + DAT_P_JT, wl, Jwl);
-      cross3(wl, Jwl, wJwl);
-      for (int c = 0; c < 3; ++c) t[c] = mom[c] - wJwl[c];
-      mv3(prm + DAT_P_JTI, t, dwl);
-      double a1[3], a2[3], a3[3], sum[3], Rs[3], dvl[3];
-      cross3(wl, xc, a1);
-      cross3(wl, a1, a2);
-      cross3(dwl, xc, a3);
-      for (int c = 0; c < 3; ++c) sum[c] = a2[c] + a3[c];
-      mv3(Rl, sum, Rs);
-      for (int c = 0; c < 3; ++c) dvl[c] = dvc[c] - Rs[c];
-      {
-        double v[3], E[9], Rn[9];
-        for (int c = 0; c < 3; ++c) v[c] = (W[c] + dw[c] * dt / 2.0) * dt;
-        exp3(v, E);
-        mm3(R, E, Rn);
-        for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-        for (int c = 0; c < 3; ++c) W[c] += dw[c] * dt;
-      }
-      for (int c = 0; c < 3; ++c) {
-        xl[c] = xl[c] + vl[c] * dt + dvl[c] * dt * dt / 2.0;
-        vl[c] = vl[c] + dvl[c] * dt;
-      }
-      {
-        double v[3], E[9], Rn[9];
-        for (int c = 0; c < 3; ++c) v[c] = (wl[c] + dwl[c] * dt / 2.0) * dt;
-        exp3(v, E);
-        mm3(Rl, E, Rn);
-        for (int k = 0; k < 9; ++k) Rl[k] = Rn[k];
-        for (int c = 0; c < 3; ++c) wl[c] += dwl[c] * dt;
-      }
-      cnt += 1;
-      if (cnt >= 20) {  // _INTEGRATION_STEPS_PER_ROTATION_PROJECTION
+      payload_accel(prm, Rl, wl, dvc, mom, dvl, dwl);
+      integrate_rot(R, W, dw, dt);
+      integrate_lin(xl, vl, dvl, dt);
+      integrate_rot(Rl, wl, dwl, dt);
+      if (projection_due(&cnt)) {
         polar3(Rl);
         polar3(R);
-        cnt = 0;
       }
       if constexpr (LOG) {
         if (s == lnext && lslot[lane] >= 0) {
@@ -1899,14 +1754,7 @@ __global__ void k_warm(KArgs a) {
     for (int k = 0; k < n; ++k)
       for (int c = 0; c < 3; ++c) s3[c] += feq[3 * k + c];
     for (int c = 0; c < N3; ++c) { a.dlamF[(size_t)sc * N3 + c] = 0.0; a.dlamM[(size_t)sc * N3 + c] = 0.0; }
-    for (int i = 0; i < n; ++i) {
-      double* pv = a.dprev + ((size_t)sc * n + i) * 9;
-      for (int c = 0; c < 3; ++c) { pv[c] = feq[3 * i + c]; pv[3 + c] = s3[c] - feq[3 * i + c]; }
-      double rf[3], jr[3];
-      cross3(prm + DAT_P_RCOM(n) + 3 * i, pv, rf);
-      mv3(prm + DAT_P_JTI, rf, jr);
-      for (int c = 0; c < 3; ++c) pv[6 + c] = -jr[c];
-    }
+    for (int i = 0; i < n; ++i) dd_fallback(prm, n, i, s3, a.dprev + ((size_t)sc * n + i) * 9);
   }
   if (a.pf)
     for (int c = 0; c < N3; ++c) a.pf[(size_t)sc * N3 + c] = feq[c];

@@ -422,6 +422,17 @@ DAT_HD void add_UDUt(double* M, PR Rtp, const double* D, double scale) {
     }
 }
 
+// DD agent i's solution (f, F, M) when its solver raised (control/rqp_dd.py:484-489), also a fresh handle's
+// "previous" solution: f = its f_eq, F = s3 - f for the caller's force sum s3, M = -JT^-1 (r_com_i x f)
+DAT_HD void dd_fallback(const double* prm, int n, int i, const double* s3, double* fFM) {
+  const double* feq = prm + DAT_P_FEQ(n);
+  for (int c = 0; c < 3; ++c) { fFM[c] = feq[3 * i + c]; fFM[3 + c] = s3[c] - feq[3 * i + c]; }
+  double rf[3], jr[3];
+  cross3(prm + DAT_P_RCOM(n) + 3 * i, fFM, rf);
+  mv3(prm + DAT_P_JTI, rf, jr);
+  for (int c = 0; c < 3; ++c) fFM[6 + c] = -jr[c];
+}
+
 // =====================================================================================
 // environment: capsule vs tree distance and CBF rows (K5)
 // =====================================================================================
@@ -509,12 +520,145 @@ DAT_HD double capsule_tree(const double* x0, const double* d, double rc, const d
   return ds - rc;
 }
 
+// The pieces of the env CBF rows (control/rqp_cadmm.py:307-373), each stated once: env_rows runs them tree after
+// tree for one solve, env_rows_coop (dat.hip) one tree per lane for the agents of a scenario.  Every
+// floating-point expression stands whole inside one piece (the rule of dat_cadmm_step.hpp), so both compute the
+// same bits.
+constexpr double ENV_TOUCH = 1e-4;  // a tree closer than this is a collision and gives no row
+
+// what every agent of a scenario shares: the payload, its stopping distance h, the capsule segment seg (from xl
+// along the velocity) and centre ctr, and reach, how far from ctr a tree's axis can be seen
+struct EnvFrame {
+  double xl[3] = {0, 0, 0}, vl[3] = {0, 0, 0}, vdir[3] = {0, 0, 0}, seg[3] = {0, 0, 0}, ctr[3] = {0, 0, 0};
+  double h = 0.0, speed = 0.0, reach = 0.0, maxdec = 1.0, rc = 0.0, deps = 0.0;
+};
+DAT_HD void env_frame(const double* prm, int n, const double* st, EnvFrame& fr) {
+  for (int c = 0; c < 3; ++c) { fr.xl[c] = st[DAT_S_XL(n) + c]; fr.vl[c] = st[DAT_S_VL(n) + c]; }
+  fr.maxdec = prm[DAT_P_MAXDEC];
+  fr.rc = prm[DAT_P_COLR];
+  fr.deps = prm[DAT_P_DISTEPS];
+  fr.reach = prm[DAT_P_VISR] + DAT_BARK_RADIUS;
+  const double v2 = dot3(fr.vl, fr.vl);
+  fr.h = 0.5 * v2 / fr.maxdec;
+  fr.speed = sqrt(v2);
+  fr.ctr[0] = fr.xl[0]; fr.ctr[1] = fr.xl[1]; fr.ctr[2] = fr.xl[2];
+  if (fr.speed != 0.0) {
+    fr.vdir[0] = fr.vl[0] / fr.speed; fr.vdir[1] = fr.vl[1] / fr.speed; fr.vdir[2] = fr.vl[2] / fr.speed;
+    fr.seg[0] = fr.h * fr.vdir[0]; fr.seg[1] = fr.h * fr.vdir[1]; fr.seg[2] = fr.h * fr.vdir[2];
+    fr.ctr[0] += 0.5 * fr.seg[0]; fr.ctr[1] += 0.5 * fr.seg[1]; fr.ctr[2] += 0.5 * fr.seg[2];
+  }
+}
+// trees are sorted by x (dat_set_forests): only the window |c.x - ctr.x| <= reach can pass the range test; its
+// first tree by binary search (the scan stops at the first tree past ctr.x + reach)
+DAT_HD int env_window_begin(const EnvFrame& fr, const double* trees, int ntree) {
+  int t0 = 0;
+  for (int len = ntree; len > 0;) {
+    int half = len >> 1;
+    if (trees[3 * (t0 + half)] < fr.ctr[0] - fr.reach) { t0 += half + 1; len -= half + 1; } else { len = half; }
+  }
+  return t0;
+}
+DAT_HD bool env_in_range(const EnvFrame& fr, const double* c) {
+  double ex = fr.ctr[0] - c[0], ey = fr.ctr[1] - c[1], ez = fr.ctr[2] - c[2];
+  return !(sqrt(ex * ex + ey * ey + ez * ez) > fr.reach);
+}
+// the tree at c: its distance dd to the capsule and the row (l3, r1) = row[0 .. 3] it produces (zero when
+// dd <= ENV_TOUCH or the payload is at rest)
+DAT_HD double env_tree_row(const EnvFrame& fr, double alpha_env, const double* c, double* row) {
+  double p1[3], p2[3];
+  const double dd = capsule_tree(fr.xl, fr.seg, fr.rc, c, p1, p2);
+  row[0] = row[1] = row[2] = row[3] = 0.0;
+  if (dd > ENV_TOUCH && fr.speed > 0.0) {
+    double rel[3] = {p1[0] - fr.xl[0], p1[1] - fr.xl[1], p1[2] - fr.xl[2]};
+    double proj = fmax(0.0, fmin(fr.h, dot3(rel, fr.vdir)));
+    double mt = sqrt(2.0 * (fr.h - proj) / fr.maxdec);
+    mt = fmax(0.0, fr.speed / fr.maxdec - mt);
+    // proj = 0 makes the two terms equal in exact arithmetic (the reference gets an exact 0);
+    // snap the rounding residue so such rows stay "0 >= rhs" like the reference's.
+    if (mt < 1e-12 * fr.speed / fr.maxdec) mt = 0.0;
+    double nr[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
+    double nn = sqrt(dot3(nr, nr));
+    nr[0] /= nn; nr[1] /= nn; nr[2] /= nn;
+    row[0] = nr[0] * mt; row[1] = nr[1] * mt; row[2] = nr[2] * mt;
+    row[3] = -alpha_env * (dd - fr.deps) - dot3(nr, fr.vl);
+  }
+  return dd;
+}
+// agent's camera (x, y) and the unit direction dir it looks along, away from the payload; false when the two
+// coincide (the reference flags a collision and emits no row)
+struct EnvCam {
+  double cam[2] = {0, 0}, dir[2] = {0, 0}, cosang = 0.0;
+};
+DAT_HD bool env_camera(const double* prm, int n, const double* st, int agent, EnvCam& k) {
+  const double* xl = st + DAT_S_XL(n);
+  double Rr[3];
+  mv3(st + DAT_S_RL(n), prm + DAT_P_R(n) + 3 * agent, Rr);
+  k.cosang = prm[DAT_P_COSCONE];
+  k.cam[0] = xl[0] + Rr[0];
+  k.cam[1] = xl[1] + Rr[1];
+  double dx = k.cam[0] - xl[0], dy = k.cam[1] - xl[1];
+  double nn = sqrt(dx * dx + dy * dy);
+  if (nn == 0.0) return false;
+  k.dir[0] = dx / nn; k.dir[1] = dy / nn;
+  return true;
+}
+// the 2-D vision cone: is the tree axis at (cx, cy) inside it
+DAT_HD bool env_in_cone(const EnvCam& k, double cx, double cy) {
+  double tx = cx - k.cam[0], ty = cy - k.cam[1];
+  double nn = sqrt(tx * tx + ty * ty);
+  return !(nn > 0.0 && (tx / nn * k.dir[0] + ty / nn * k.dir[1]) < k.cosang);
+}
+// The trees one solve sees, the DAT_NENV nearest in order of distance: slot j holds the distance bd[j] and the
+// row lhs[j] . dvl >= rhs[j].  All slot indices are compile-time so the rows stay in registers.
+struct EnvSeen {
+  double bd[DAT_NENV], dmin = 1e300;
+  int cnt = 0;
+};
+DAT_HD void env_clear(EnvSeen& s, double lhs[DAT_NENV][3], double rhs[DAT_NENV]) {
+#pragma unroll
+  for (int j = 0; j < DAT_NENV; ++j) { s.bd[j] = 1e300; lhs[j][0] = lhs[j][1] = lhs[j][2] = 0.0; rhs[j] = 0.0; }
+}
+// a seen tree at distance dd with row (l3, r1) = row[0 .. 3]: sorted insertion at
+// position = number of kept entries with distance <= dd (ties keep arrival order).  The caller flags the collision
+// (dd < ENV_TOUCH) and writes its EnvOut itself: with the pieces writing EnvOut through a reference k_env_class
+// spills 732 - 1148 B per lane where it now spills 88.
+DAT_HD void env_see(EnvSeen& s, double dd, const double* row, double lhs[DAT_NENV][3],
+                    double rhs[DAT_NENV]) {
+  s.dmin = fmin(s.dmin, dd);
+  ++s.cnt;
+  int pos = 0;
+#pragma unroll
+  for (int j = 0; j < DAT_NENV; ++j) pos += (s.bd[j] <= dd) ? 1 : 0;
+  if (pos >= DAT_NENV) return;
+#pragma unroll
+  for (int j = DAT_NENV - 1; j >= 1; --j) {
+    if (j > pos) {
+      s.bd[j] = s.bd[j - 1];
+      lhs[j][0] = lhs[j - 1][0]; lhs[j][1] = lhs[j - 1][1]; lhs[j][2] = lhs[j - 1][2];
+      rhs[j] = rhs[j - 1];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < DAT_NENV; ++j) {
+    if (j == pos) {
+      s.bd[j] = dd;
+      lhs[j][0] = row[0]; lhs[j][1] = row[1]; lhs[j][2] = row[2];
+      rhs[j] = row[3];
+    }
+  }
+}
+// bit j of *mask is set when the reference emits the row of slot j (a tree closer than ENV_TOUCH leaves it zero)
+DAT_HD unsigned env_mask(const EnvSeen& s) {
+  unsigned m = 0u;
+#pragma unroll
+  for (int j = 0; j < DAT_NENV; ++j)
+    if (s.bd[j] < 1e299 && s.bd[j] > ENV_TOUCH) m |= 1u << j;
+  return m;
+}
+
 // Env CBF rows of one solve (control/rqp_cadmm.py:307-373; camera == none selects the centralized
 // query without vision cone, rqp_centralized.py:280-337).  Tree selection: distance of the capsule
-// centre to tree_pos <= vision_r + bark radius, plus the 2-D cone test for distributed agents; the
-// DAT_NENV nearest selected trees fill the slots in order of distance.  Slot j carries the row
-// lhs[j] . dvl >= rhs[j]; bit j of *mask is set when the reference emits that row (a tree closer
-// than 1e-4 leaves it zero).  All slot indices are compile-time so the rows stay in registers.
+// centre to tree_pos <= vision_r + bark radius, plus the 2-D cone test for distributed agents.
 DAT_HD EnvOut env_rows(const double* prm, int n, const double* st, const double* trees, int ntree,
                        int agent /* -1: centralized */, double alpha_env, unsigned* mask, double lhs[DAT_NENV][3],
                        double rhs[DAT_NENV]) {
@@ -522,112 +666,29 @@ DAT_HD EnvOut env_rows(const double* prm, int n, const double* st, const double*
   out.collision = 0;
   out.min_env_dist = prm[DAT_P_VISR];
   *mask = 0u;
-#pragma unroll
-  for (int j = 0; j < DAT_NENV; ++j) { lhs[j][0] = lhs[j][1] = lhs[j][2] = 0.0; rhs[j] = 0.0; }
+  EnvSeen seen;
+  env_clear(seen, lhs, rhs);
   if (trees == nullptr || ntree <= 0) return out;
-  const double* xl = st + DAT_S_XL(n);
-  const double* vl = st + DAT_S_VL(n);
-  const double* Rl = st + DAT_S_RL(n);
-  const double maxdec = prm[DAT_P_MAXDEC], visr = prm[DAT_P_VISR], rc = prm[DAT_P_COLR];
-  const double deps = prm[DAT_P_DISTEPS];
-  double v2 = dot3(vl, vl);
-  double h = 0.5 * v2 / maxdec;
-  double speed = sqrt(v2);
-  double vdir[3] = {0, 0, 0}, seg[3] = {0, 0, 0}, ctr[3] = {xl[0], xl[1], xl[2]};
-  if (speed != 0.0) {
-    vdir[0] = vl[0] / speed; vdir[1] = vl[1] / speed; vdir[2] = vl[2] / speed;
-    seg[0] = h * vdir[0]; seg[1] = h * vdir[1]; seg[2] = h * vdir[2];
-    ctr[0] += 0.5 * seg[0]; ctr[1] += 0.5 * seg[1]; ctr[2] += 0.5 * seg[2];
+  EnvFrame fr;
+  env_frame(prm, n, st, fr);
+  EnvCam cam;
+  if (agent >= 0 && !env_camera(prm, n, st, agent, cam)) {
+    out.collision = 1;
+    return out;
   }
-  double cam[2] = {0, 0}, dir[2] = {0, 0}, cosang = prm[DAT_P_COSCONE];
-  if (agent >= 0) {
-    const double* r = prm + DAT_P_R(n) + 3 * agent;
-    double Rr[3];
-    mv3(Rl, r, Rr);
-    cam[0] = xl[0] + Rr[0];
-    cam[1] = xl[1] + Rr[1];
-    double dx = cam[0] - xl[0], dy = cam[1] - xl[1];
-    double nn = sqrt(dx * dx + dy * dy);
-    if (nn == 0.0) {
-      out.collision = 1;
-      return out;
-    }
-    dir[0] = dx / nn; dir[1] = dy / nn;
-  }
-  // sorted insertion of (distance, row) into the DAT_NENV slots
-  double bd[DAT_NENV];
-#pragma unroll
-  for (int j = 0; j < DAT_NENV; ++j) bd[j] = 1e300;
-  int cnt = 0;
-  double dmin = 1e300;
-  // trees are sorted by x (dat_set_forests): only the window |c.x - ctr.x| <= visr + bark radius
-  // can pass the range test below; lower bound by binary search, stop past the upper edge
-  const double reach = visr + DAT_BARK_RADIUS;
-  int t0 = 0;
-  for (int len = ntree; len > 0;) {
-    int half = len >> 1;
-    if (trees[3 * (t0 + half)] < ctr[0] - reach) { t0 += half + 1; len -= half + 1; } else { len = half; }
-  }
-  for (int t = t0; t < ntree; ++t) {
+  for (int t = env_window_begin(fr, trees, ntree); t < ntree; ++t) {
     const double* c = trees + 3 * t;
-    if (c[0] > ctr[0] + reach) break;
-    double ex = ctr[0] - c[0], ey = ctr[1] - c[1], ez = ctr[2] - c[2];
-    if (sqrt(ex * ex + ey * ey + ez * ez) > visr + DAT_BARK_RADIUS) continue;
-    if (agent >= 0) {
-      double tx = c[0] - cam[0], ty = c[1] - cam[1];
-      double nn = sqrt(tx * tx + ty * ty);
-      if (nn > 0.0 && (tx / nn * dir[0] + ty / nn * dir[1]) < cosang) continue;
-    }
-    double p1[3], p2[3];
-    double dd = capsule_tree(xl, seg, rc, c, p1, p2);
-    if (dd < 1e-4) out.collision = 1;
-    dmin = fmin(dmin, dd);
-    ++cnt;
-    // the row this tree produces (zero when dd <= 1e-4 or the payload is at rest)
-    double l3[3] = {0, 0, 0}, r1 = 0.0;
-    if (dd > 1e-4 && speed > 0.0) {
-      double rel[3] = {p1[0] - xl[0], p1[1] - xl[1], p1[2] - xl[2]};
-      double proj = fmax(0.0, fmin(h, dot3(rel, vdir)));
-      double mt = sqrt(2.0 * (h - proj) / maxdec);
-      mt = fmax(0.0, speed / maxdec - mt);
-      // proj = 0 makes the two terms equal in exact arithmetic (the reference gets an exact 0);
-      // snap the rounding residue so such rows stay "0 >= rhs" like the reference's.
-      if (mt < 1e-12 * speed / maxdec) mt = 0.0;
-      double nr[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-      double nn = sqrt(dot3(nr, nr));
-      nr[0] /= nn; nr[1] /= nn; nr[2] /= nn;
-      l3[0] = nr[0] * mt; l3[1] = nr[1] * mt; l3[2] = nr[2] * mt;
-      r1 = -alpha_env * (dd - deps) - dot3(nr, vl);
-    }
-    // position = number of kept entries with distance <= dd (ties keep arrival order)
-    int pos = 0;
-#pragma unroll
-    for (int j = 0; j < DAT_NENV; ++j) pos += (bd[j] <= dd) ? 1 : 0;
-    if (pos >= DAT_NENV) continue;
-#pragma unroll
-    for (int j = DAT_NENV - 1; j >= 1; --j) {
-      if (j > pos) {
-        bd[j] = bd[j - 1];
-        lhs[j][0] = lhs[j - 1][0]; lhs[j][1] = lhs[j - 1][1]; lhs[j][2] = lhs[j - 1][2];
-        rhs[j] = rhs[j - 1];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < DAT_NENV; ++j) {
-      if (j == pos) {
-        bd[j] = dd;
-        lhs[j][0] = l3[0]; lhs[j][1] = l3[1]; lhs[j][2] = l3[2];
-        rhs[j] = r1;
-      }
-    }
+    if (c[0] > fr.ctr[0] + fr.reach) break;
+    if (!env_in_range(fr, c)) continue;
+    if (agent >= 0 && !env_in_cone(cam, c[0], c[1])) continue;
+    double row[4];
+    const double dd = env_tree_row(fr, alpha_env, c, row);
+    if (dd < ENV_TOUCH) out.collision = 1;
+    env_see(seen, dd, row, lhs, rhs);
   }
-  if (cnt > 0 && speed > 0.0) {
-    out.min_env_dist = dmin;
-    unsigned m = 0u;
-#pragma unroll
-    for (int j = 0; j < DAT_NENV; ++j)
-      if (bd[j] < 1e299 && bd[j] > 1e-4) m |= 1u << j;
-    *mask = m;
+  if (seen.cnt > 0 && fr.speed > 0.0) {
+    out.min_env_dist = seen.dmin;
+    *mask = env_mask(seen);
   }
   return out;
 }
@@ -692,82 +753,95 @@ DAT_HD void ll_control_agent(const double* R, const double* w, const double* J, 
   for (int c = 0; c < 3; ++c) M[c] = -kR * eR[c] - kW * w[c] + wJw[c];
 }
 
-// One simulation step of one scenario: LL control from f_des, forward dynamics, integration
-// (system/rigid_quadrotor_payload.py:173-222, 129-148).  counter: steps since the last projection.
-template <int NMAX>
-DAT_HD void sim_step(const double* prm, int n, double* st, int* counter, const double* fdes, double dt,
-                     int ll_kind = LL_PD) {
-  double* R = st + DAT_S_R(n);
-  double* W = st + DAT_S_W(n);
-  double* xl = st + DAT_S_XL(n);
-  double* vl = st + DAT_S_VL(n);
-  double* Rl = st + DAT_S_RL(n);
-  double* wl = st + DAT_S_WL(n);
+// The pieces of a simulation step (system/rigid_quadrotor_payload.py:173-222, 129-148), each stated once: sim_step
+// runs them agent after agent, k_rollout_agents one agent per lane with the force / moment sums through LDS, rp_step
+// the payload's.  Every floating-point expression stands whole inside one piece (the rule of dat_cadmm_step.hpp), so
+// the callers compute the same bits.
+// dw = Ji (M - w x J w): a rigid body's angular acceleration under the moment M
+DAT_HD void rot_accel(const double* J, const double* Ji, const double* w, const double* M, double* dw) {
+  double Jw[3], wJw[3], t[3];
+  mv3(J, w, Jw);
+  cross3(w, Jw, wJw);
+  for (int c = 0; c < 3; ++c) t[c] = M[c] - wJw[c];
+  mv3(Ji, t, dw);
+}
+// one quadrotor under thrust f and moment M: its angular acceleration dw and what it adds to the payload's force
+// and moment sums, um = (f R e3, hat(r_com) Rl' f R e3)
+DAT_HD void quad_accel(const double* R, const double* W, const double* J, const double* Ji, const double* rcom_i,
+                       const double* Rl, double f, const double* M, double* dw, double* um) {
+  rot_accel(J, Ji, W, M, dw);
+  um[0] = R[2] * f; um[1] = R[5] * f; um[2] = R[8] * f;
+  double ub[3];
+  mtv3(Rl, um, ub);
+  cross3(rcom_i, ub, um + 3);
+}
+// the payload under the summed agent forces dvc and moments mom: dvl = dv_com - Rl (hat(wl)^2 + hat(dwl)) x_com
+DAT_HD void payload_accel(const double* prm, const double* Rl, const double* wl, const double* dvc,
+                          const double* mom, double* dvl, double* dwl) {
   const double mT = prm[DAT_P_MT];
   const double* xc = prm + DAT_P_XCOM;
-  const double* JT = prm + DAT_P_JT;
-  const double* JTi = prm + DAT_P_JTI;
-  const double* rcom = prm + DAT_P_RCOM(n);
-  const double* J = prm + DAT_P_J(n);
-  const double* Ji = prm + DAT_P_JINV(n);
-  double dvc[3] = {0, 0, 0}, mom[3] = {0, 0, 0};
-  double dw[NMAX][3];
-  for (int i = 0; i < n; ++i) {
-    double f, M[3];
-    ll_control_agent(R + 9 * i, W + 3 * i, J + 9 * i, fdes + 3 * i, &f, M, ll_kind);
-    double Jw[3], wJw[3], t[3];
-    mv3(J + 9 * i, W + 3 * i, Jw);
-    cross3(W + 3 * i, Jw, wJw);
-    for (int c = 0; c < 3; ++c) t[c] = M[c] - wJw[c];
-    mv3(Ji + 9 * i, t, dw[i]);
-    double u[3] = {R[9 * i + 2] * f, R[9 * i + 5] * f, R[9 * i + 8] * f};  // f R e3
-    dvc[0] += u[0]; dvc[1] += u[1]; dvc[2] += u[2];
-    double ub[3], m3[3];
-    mtv3(Rl, u, ub);
-    cross3(rcom + 3 * i, ub, m3);
-    mom[0] += m3[0]; mom[1] += m3[1]; mom[2] += m3[2];
-  }
-  for (int c = 0; c < 3; ++c) dvc[c] /= mT;
-  dvc[2] -= DAT_GRAVITY;
-  double Jwl[3], wJwl[3], t[3], dwl[3];
-  mv3(JT, wl, Jwl);
-  cross3(wl, Jwl, wJwl);
-  for (int c = 0; c < 3; ++c) t[c] = mom[c] - wJwl[c];
-  mv3(JTi, t, dwl);
-  // dvl = dv_com - Rl (hat(wl)^2 + hat(dwl)) x_com
-  double a1[3], a2[3], a3[3], sum[3], Rs[3], dvl[3];
+  double dv[3];
+  for (int c = 0; c < 3; ++c) dv[c] = dvc[c] / mT;
+  dv[2] -= DAT_GRAVITY;
+  rot_accel(prm + DAT_P_JT, prm + DAT_P_JTI, wl, mom, dwl);
+  double a1[3], a2[3], a3[3], sum[3], Rs[3];
   cross3(wl, xc, a1);
   cross3(wl, a1, a2);
   cross3(dwl, xc, a3);
   for (int c = 0; c < 3; ++c) sum[c] = a2[c] + a3[c];
   mv3(Rl, sum, Rs);
-  for (int c = 0; c < 3; ++c) dvl[c] = dvc[c] - Rs[c];
-  // integrate
-  for (int i = 0; i < n; ++i) {
-    double v[3], E[9], Rn[9];
-    for (int c = 0; c < 3; ++c) v[c] = (W[3 * i + c] + dw[i][c] * dt / 2.0) * dt;
-    exp3(v, E);
-    mm3(R + 9 * i, E, Rn);
-    for (int c = 0; c < 9; ++c) R[9 * i + c] = Rn[c];
-    for (int c = 0; c < 3; ++c) W[3 * i + c] += dw[i][c] * dt;
-  }
+  for (int c = 0; c < 3; ++c) dvl[c] = dv[c] - Rs[c];
+}
+// Lie midpoint step of an attitude: R <- R exp((W + dw dt / 2) dt), W <- W + dw dt
+DAT_HD void integrate_rot(double* R, double* W, const double* dw, double dt) {
+  double v[3], E[9], Rn[9];
+  for (int c = 0; c < 3; ++c) v[c] = (W[c] + dw[c] * dt / 2.0) * dt;
+  exp3(v, E);
+  mm3(R, E, Rn);
+  for (int c = 0; c < 9; ++c) R[c] = Rn[c];
+  for (int c = 0; c < 3; ++c) W[c] += dw[c] * dt;
+}
+DAT_HD void integrate_lin(double* xl, double* vl, const double* dvl, double dt) {
   for (int c = 0; c < 3; ++c) {
     xl[c] = xl[c] + vl[c] * dt + dvl[c] * dt * dt / 2.0;
     vl[c] = vl[c] + dvl[c] * dt;
   }
-  {
-    double v[3], E[9], Rn[9];
-    for (int c = 0; c < 3; ++c) v[c] = (wl[c] + dwl[c] * dt / 2.0) * dt;
-    exp3(v, E);
-    mm3(Rl, E, Rn);
-    for (int c = 0; c < 9; ++c) Rl[c] = Rn[c];
-    for (int c = 0; c < 3; ++c) wl[c] += dwl[c] * dt;
+}
+// counts a step; true when the rotations are due their polar3 projection (every
+// _INTEGRATION_STEPS_PER_ROTATION_PROJECTION = 20 steps; system/rigid_payload.py:11 has the same)
+DAT_HD bool projection_due(int* counter) {
+  if (++*counter < 20) return false;
+  *counter = 0;
+  return true;
+}
+
+// One simulation step of one scenario: LL control from f_des, forward dynamics, integration.
+// counter: steps since the last projection.
+template <int NMAX>
+DAT_HD void sim_step(const double* prm, int n, double* st, int* counter, const double* fdes, double dt,
+                     int ll_kind = LL_PD) {
+  double* R = st + DAT_S_R(n);
+  double* W = st + DAT_S_W(n);
+  double* Rl = st + DAT_S_RL(n);
+  double* wl = st + DAT_S_WL(n);
+  const double* J = prm + DAT_P_J(n);
+  double dvc[3] = {0, 0, 0}, mom[3] = {0, 0, 0};
+  double dw[NMAX][3];
+  for (int i = 0; i < n; ++i) {
+    double f, M[3], um[6];
+    ll_control_agent(R + 9 * i, W + 3 * i, J + 9 * i, fdes + 3 * i, &f, M, ll_kind);
+    quad_accel(R + 9 * i, W + 3 * i, J + 9 * i, prm + DAT_P_JINV(n) + 9 * i, prm + DAT_P_RCOM(n) + 3 * i, Rl, f, M,
+               dw[i], um);
+    for (int c = 0; c < 3; ++c) { dvc[c] += um[c]; mom[c] += um[3 + c]; }
   }
-  *counter += 1;
-  if (*counter >= 20) {  // _INTEGRATION_STEPS_PER_ROTATION_PROJECTION
+  double dvl[3], dwl[3];
+  payload_accel(prm, Rl, wl, dvc, mom, dvl, dwl);
+  for (int i = 0; i < n; ++i) integrate_rot(R + 9 * i, W + 3 * i, dw[i], dt);
+  integrate_lin(st + DAT_S_XL(n), st + DAT_S_VL(n), dvl, dt);
+  integrate_rot(Rl, wl, dwl, dt);
+  if (projection_due(counter)) {
     polar3(Rl);
     for (int i = 0; i < n; ++i) polar3(R + 9 * i);
-    *counter = 0;
   }
 }
 
@@ -776,13 +850,9 @@ DAT_HD void sim_step(const double* prm, int n, double* st, int* counter, const d
 // payload part of a dat state block with the rigid-payload parameter block (mT = ml, JT = Jl,
 // r_com = r): ml dvl = sum f - ml g e3, Jl dwl + wl x Jl wl = sum hat(r_i) Rl' f_i.
 DAT_HD void rp_step(const double* prm, int n, double* st, int* counter, const double* f, double dt) {
-  double* xl = st + DAT_S_XL(n);
-  double* vl = st + DAT_S_VL(n);
   double* Rl = st + DAT_S_RL(n);
   double* wl = st + DAT_S_WL(n);
   const double ml = prm[DAT_P_MT];
-  const double* Jl = prm + DAT_P_JT;
-  const double* Jli = prm + DAT_P_JTI;
   const double* r = prm + DAT_P_RCOM(n);
   double F[3] = {0, 0, 0}, Mo[3] = {0, 0, 0};
   for (int i = 0; i < n; ++i) {
@@ -791,27 +861,11 @@ DAT_HD void rp_step(const double* prm, int n, double* st, int* counter, const do
     cross3(r + 3 * i, fb, m3);
     for (int c = 0; c < 3; ++c) { F[c] += f[3 * i + c]; Mo[c] += m3[c]; }
   }
-  double dvl[3] = {F[0] / ml, F[1] / ml, F[2] / ml - DAT_GRAVITY};
-  double Jw[3], wJw[3], t[3], dwl[3];
-  mv3(Jl, wl, Jw);
-  cross3(wl, Jw, wJw);
-  for (int c = 0; c < 3; ++c) t[c] = Mo[c] - wJw[c];
-  mv3(Jli, t, dwl);
-  for (int c = 0; c < 3; ++c) {
-    xl[c] = xl[c] + vl[c] * dt + dvl[c] * dt * dt / 2.0;
-    vl[c] = vl[c] + dvl[c] * dt;
-  }
-  double v[3], E[9], Rn[9];
-  for (int c = 0; c < 3; ++c) v[c] = (wl[c] + dwl[c] * dt / 2.0) * dt;
-  exp3(v, E);
-  mm3(Rl, E, Rn);
-  for (int c = 0; c < 9; ++c) Rl[c] = Rn[c];
-  for (int c = 0; c < 3; ++c) wl[c] += dwl[c] * dt;
-  *counter += 1;
-  if (*counter >= 20) {  // _INTEGRATION_STEPS_PER_ROTATION_PROJECTION (system/rigid_payload.py:11)
-    polar3(Rl);
-    *counter = 0;
-  }
+  double dvl[3] = {F[0] / ml, F[1] / ml, F[2] / ml - DAT_GRAVITY}, dwl[3];
+  rot_accel(prm + DAT_P_JT, prm + DAT_P_JTI, wl, Mo, dwl);
+  integrate_lin(st + DAT_S_XL(n), st + DAT_S_VL(n), dvl, dt);
+  integrate_rot(Rl, wl, dwl, dt);
+  if (projection_due(counter)) polar3(Rl);
 }
 
 // x_ref, v_ref of _desired_acceleration_forest (example/rqp_example.py:36-48) at the payload position xl: the
