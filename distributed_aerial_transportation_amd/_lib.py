@@ -160,6 +160,7 @@ EXPORTS = {
     "dat_get_stream_count": (ctypes.c_int, [H]),
     "dat_get_advance_counts": (ctypes.c_int, [H, LL, LL]),
     "dat_debug_advance_split": (ctypes.c_int, [H, U8]),
+    "dat_debug_get_env_class": (ctypes.c_int, [H, D, D, I, I]),
     "dat_get_step_marks": (ctypes.c_int, [H, D, ctypes.c_int]),
     "dat_get_counters": (ctypes.c_int, [H, LL, LL, LL, LL, D]),
     "dat_get_class_counters": (ctypes.c_int, [H, ctypes.c_int, LL, LL, LL, D]),

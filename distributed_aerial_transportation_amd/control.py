@@ -243,6 +243,17 @@ class BatchedController:
             raise ValueError("early_mask must have one entry per scenario")
         L.check(self._lib.dat_debug_advance_split(self._h, L.ptr(m, L.U8)))
 
+    def debug_env_class(self):
+        """dat_debug_get_env_class (tests): the env rows the last control step's k_cadmm consumed, as env_rows
+        reports them -- (lhs (B, n, 10, 3), rhs (B, n, 10), nrow (B, n)) -- and the scenarios' env class (B,)."""
+        B, n = self.batch, self.n
+        lhs = np.empty((B, n, layout.NENV, 3))
+        rhs = np.empty((B, n, layout.NENV))
+        nr = np.empty((B, n), dtype=np.int32)
+        cls = np.empty(B, dtype=np.int32)
+        L.check(self._lib.dat_debug_get_env_class(self._h, L.ptr(lhs), L.ptr(rhs), L.ptr(nr, L.I), L.ptr(cls, L.I)))
+        return lhs, rhs, nr, cls
+
     def closed_loop(self, hl_steps: int) -> None:
         L.check(self._lib.dat_closed_loop(self._h, int(hl_steps)))
 

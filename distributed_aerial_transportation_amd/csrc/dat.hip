@@ -243,7 +243,7 @@ __device__ inline int env_class_of(unsigned emask, const double lhs[DAT_NENV][3]
 // chunk of n candidates -- range test, capsule_tree distance and the CBF row, once per tree instead
 // of once per agent that sees it -- and publishes them in LDS; then every lane runs its own cone
 // filter and sorted insertion over the chunk in tree order.  The pieces and the insertion order are env_rows',
-// so the rows are bitwise identical by construction (test_gpu_env_rows / test_gpu_c4 check it).
+// so the rows are bitwise identical by construction (test_gpu_env_rows_reference.py checks it).
 // Must be called by every lane of the block (barriers inside).
 constexpr int ENV_CE = 8;  // published entry: in range, c.x, c.y, dd, l3[3], r1
 // LDS stride of a published entry: 9 doubles (18 dwords), so the 32 lanes of a ds_*_b64 half-wave
@@ -1960,6 +1960,7 @@ struct dat_handle {
   int *need = nullptr, *slist = nullptr, *scount = nullptr, *ipmx = nullptr;
   double* erows = nullptr;     // C-ADMM: env rows of the step, k_env_class -> k_cadmm
   unsigned* emask = nullptr;
+  int env_sub = 0;             // sub-batches the last step's k_env_class ran on (the block layout of erows; 0: no step yet)
   long long hl_steps = 0;
   double hl_ms = 0.0;
   // host clock marks of the last dat_closed_loop call: its start, then each HL step's k_cadmm / k_dd /
@@ -2957,6 +2958,7 @@ int dat_control_step(dat_handle* h, const double* state, const double* acc_des, 
   const size_t B = h->cfg.batch;
   if (state) HIPCHK(hipMemcpyAsync(h->state, state, sizeof(double) * B * h->S, hipMemcpyHostToDevice, h->stream));
   const Sub u = sub_batch(h);
+  h->env_sub = 1;
   if (acc_des) {
     HIPCHK(hipMemcpyAsync(h->acc, acc_des, sizeof(double) * B * 6, hipMemcpyHostToDevice, h->stream));
   } else {
@@ -2987,6 +2989,7 @@ int dat_control_steps(dat_handle* h, int steps, const double* acc_seq, double* f
   }
   HIPCHK(hipMemcpyAsync(h->acc_seq, acc_seq, sizeof(double) * need, hipMemcpyHostToDevice, h->stream));
   Sub u = sub_batch(h);
+  h->env_sub = 1;
   u.a.ksteps = steps;
   u.a.acc = h->acc_seq;
   if (launch_step(h, u)) return -1;
@@ -3036,6 +3039,7 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
   if (!h) return fail("null handle");
   if (log_admit(h, hl_steps) || step_entry(h)) return -1;
   const int S = h->nsub;
+  if (hl_steps > 0) h->env_sub = S;
   if (hl_steps > 0 && pipeline_ready(h)) return closed_loop_pipelined(h, hl_steps);
   const bool overlap = advance_ready(h);
   const size_t ndrain = S > 1 && hl_steps > 0 ? (size_t)S * hl_steps : 0;
@@ -3228,6 +3232,42 @@ int dat_debug_advance_split(dat_handle* h, const unsigned char* early_mask) {
   if (!h->advmask && dalloc(h, &h->advmask, (size_t)h->cfg.batch)) return -1;
   HIPCHK(hipMemcpyAsync(h->advmask, early_mask, (size_t)h->cfg.batch, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dat_debug_get_env_class(dat_handle* h, double* lhs, double* rhs, int* nrow, int* env_class) {
+  if (!h || !lhs || !rhs || !nrow || !env_class) return fail("dat_debug_get_env_class: null argument");
+  if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_debug_get_env_class: C-ADMM handles only");
+  if (h->env_sub < 1) return fail("dat_debug_get_env_class: no control step has run");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipStream_t st : h->streams) HIPCHK(hipStreamSynchronize(st));  // (the handle's own among them)
+  const size_t B = h->cfg.batch, n = h->cfg.n, per = (size_t)4 * DAT_NENV * n;
+  std::vector<double> img(B * per);
+  std::vector<unsigned> mask(B * n);
+  std::vector<int> need(B);
+  HIPCHK(hipMemcpy(img.data(), h->erows, sizeof(double) * img.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(mask.data(), h->emask, sizeof(unsigned) * mask.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(need.data(), h->need, sizeof(int) * need.size(), hipMemcpyDeviceToHost));
+  std::fill(lhs, lhs + B * n * DAT_NENV * 3, 0.0);
+  std::fill(rhs, rhs + B * n * DAT_NENV, 0.0);
+  const int S = h->env_sub;
+  for (int s = 0; s < S; ++s) {  // the sub-batch's block of the image (sub_batch, sub_kargs): stride Bs n
+    const size_t off = (size_t)((long long)B * s / S), NA = ((size_t)((long long)B * (s + 1) / S) - off) * n;
+    const double* blk = img.data() + per * off;
+    for (size_t g = 0; g < NA; ++g) {
+      const size_t t = off * n + g;  // scenario-major index of the agent in the whole batch
+      const unsigned m = mask[t];
+      int k = 0;
+      for (int j = 0; j < DAT_NENV; ++j) {
+        if (!((m >> j) & 1u)) continue;
+        for (int c = 0; c < 3; ++c) lhs[(t * DAT_NENV + k) * 3 + c] = blk[(4 * j + c) * NA + g];
+        rhs[t * DAT_NENV + k] = blk[(4 * j + 3) * NA + g];
+        ++k;
+      }
+      nrow[t] = k;
+    }
+  }
+  for (size_t sc = 0; sc < B; ++sc) env_class[sc] = need[sc] >= NKEY ? need[sc] - NKEY : need[sc] / NIB;
   return 0;
 }
 

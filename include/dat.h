@@ -178,6 +178,12 @@ int dat_get_advance_counts(dat_handle* h, long long* early, long long* late);
  * ended and lets it take exactly the scenarios with early_mask[sc] != 0: a split between the two passes that
  * does not depend on timing.  Null clears it. */
 int dat_debug_advance_split(dat_handle* h, const unsigned char* early_mask);
+/* Test hook (C-ADMM): what the most recent step's k_env_class left in the handle, read after a control step with a
+ * forest set (dat_control_step, or the last step of dat_closed_loop).  Launches nothing: waits for the handle's
+ * streams and copies out the env rows k_cadmm consumed, decoded from their device image (per agent the marked
+ * slots compacted in slot order, the rest zero, as dat_env_rows reports its rows), and per scenario the env class
+ * of its sort key.  lhs: batch x n x 10 x 3, rhs: batch x n x 10, nrow: batch x n, env_class: batch. */
+int dat_debug_get_env_class(dat_handle* h, double* lhs, double* rhs, int* nrow, int* env_class);
 /* Host steady-clock marks (ms) of the last dat_closed_loop call: [0] its start (0.0), then the completion
  * of each HL step's control kernel; consecutive differences are per-step times of the back-to-back run.
  * Writes up to max_marks values; returns the number of marks (hl_steps + 1).  With sub-batch streams
