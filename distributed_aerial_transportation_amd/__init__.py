@@ -13,7 +13,7 @@ from . import rigid_payload  # noqa: F401  (RPCentralizedController / RPDynamics
 
 def __getattr__(name):
     # controllers load libdat.so lazily so that data-only imports work without a GPU
-    if name in ("BatchedController", "RQPCentralizedController", "RQPCADMMController", "RQPDDController",
+    if name in ("BatchedController", "Checkpoint", "RQPCentralizedController", "RQPCADMMController", "RQPDDController",
                 "RQPClosedLoop", "SolverStatistics", "StepResult", "RQPCADMMPrimalSolver", "RQPDDPrimalSolver", "RQPLowLevelController"):
         from . import control
 

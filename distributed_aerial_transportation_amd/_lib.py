@@ -28,6 +28,7 @@ OBJ_DIR = os.path.join(PKG, "build")
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on"]
 DEPS = [SRC, SRC_CENT, SRC_COMM, os.path.join(PKG, "csrc", "dat_core.hpp"), os.path.join(PKG, "csrc", "dat_qp.hpp"),
         os.path.join(PKG, "csrc", "dat_cadmm_step.hpp"), os.path.join(PKG, "csrc", "dat_kargs.hpp"),
+        os.path.join(PKG, "csrc", "dat_ckpt.hpp"),
         os.path.join(PKG, "csrc", "dat_layout.h"), os.path.join(REPO, "include", "dat.h")]
 
 MODE_CENTRALIZED, MODE_CADMM, MODE_DD = 0, 1, 2
@@ -150,6 +151,10 @@ EXPORTS = {
     "dat_reset_warm_start": (ctypes.c_int, [H]),
     "dat_set_state": (ctypes.c_int, [H, D, I]),
     "dat_get_state": (ctypes.c_int, [H, D, I]),
+    "dat_checkpoint_bytes": (ctypes.c_int, [H, ctypes.c_int, LL]),
+    "dat_checkpoint_save": (ctypes.c_int, [H, I, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),
+    "dat_checkpoint_load": (ctypes.c_int, [H, ctypes.c_void_p, ctypes.c_longlong, I, I, ctypes.c_int]),
+    "dat_get_checkpoint_ms": (ctypes.c_int, [H, D, D]),
     "dat_control_step": (ctypes.c_int, [H, D, D, D, I, I, D, U8, D]),
     "dat_rollout": (ctypes.c_int, [H, ctypes.c_int, D]),
     "dat_closed_loop": (ctypes.c_int, [H, ctypes.c_int]),

@@ -60,6 +60,104 @@ class StepResult:
     gpu_ms: float = 0.0
 
 
+class Checkpoint:
+    """Checkpoint records of ``count`` scenarios of one controller type (``mode``: DAT_MODE_*) and team size ``n``:
+    the blob of dat_checkpoint_save (include/dat.h; layout: csrc/dat_layout.h, DAT_CK_*).  Each record holds the
+    scenario's state and polar counter, f_des, the previous step's pass counts and the controller's warm state.
+    Host data only: ``BatchedController.checkpoint`` makes one, ``BatchedController.restore`` writes records back
+    into scenarios of any handle of the same mode and n."""
+
+    # the record's arrays under the reference's names, with their shapes per scenario (n -> shape), agent-major
+    _NAMES = {"state": ("state", lambda n: (layout.state_size(n),)), "fdes": ("f_des", lambda n: (n, 3)),
+              "cf": ("f", lambda n: (n, n, 3)), "cfbar": ("f_mean", lambda n: (n, 3)),
+              "clam": ("lambda_f", lambda n: (n, n, 3)), "dlamF": ("lambda_F", lambda n: (n, 3)),
+              "dlamM": ("lambda_M", lambda n: (n, 3)), "dprev": ("prev", lambda n: (n, 9)),
+              "pf": ("prev_f", lambda n: (n, 3))}
+
+    def __init__(self, data, copy: bool = True) -> None:
+        """data: a blob (bytes-like, or a contiguous numpy array); copy=False adopts a writable array as it is."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1).view(np.uint8)
+        if copy or not buf.flags.writeable:
+            buf = np.array(buf, dtype=np.uint8, copy=True)
+        H = layout.CK_H
+        if buf.size < layout.CK_HEADER_BYTES:
+            raise ValueError(f"checkpoint: {buf.size} bytes are shorter than the {layout.CK_HEADER_BYTES}-byte header")
+        hdr = buf[: layout.CK_HEADER_BYTES]
+        if int(hdr[H["MAGIC"]: H["MAGIC"] + 8].view(np.uint64)[0]) != layout.CK_MAGIC:
+            raise ValueError("checkpoint: bad magic (not a checkpoint)")
+        version, mode, n, words = (int(v) for v in hdr[H["VERSION"]: H["VERSION"] + 16].view(np.int32))
+        count = int(hdr[H["COUNT"]: H["COUNT"] + 8].view(np.int64)[0])
+        if version != layout.CK_VERSION:
+            raise ValueError(f"checkpoint: format version {version}, this package reads version {layout.CK_VERSION}")
+        if mode not in layout.CK_MODES:
+            raise ValueError(f"checkpoint: bad mode {mode}")
+        if not 3 <= n <= 16:
+            raise ValueError(f"checkpoint: bad n = {n}")
+        if words != layout.ck_words(mode, n):
+            raise ValueError(f"checkpoint: {words} words per record, mode {mode} at n = {n} has "
+                             f"{layout.ck_words(mode, n)}")
+        if hdr[H["PAD"]:].any():
+            raise ValueError("checkpoint: header padding is not zero")
+        if count < 0 or buf.size != layout.CK_HEADER_BYTES + count * words * 8:
+            raise ValueError(f"checkpoint: {buf.size} bytes, the header's {count} records take "
+                             f"{layout.CK_HEADER_BYTES + count * words * 8}")
+        self.mode, self.n, self.count, self.words = mode, n, count, words
+        self._buf = buf
+
+    @staticmethod
+    def header(mode: int, n: int, count: int) -> np.ndarray:
+        """The 64-byte header of a blob of `count` records."""
+        H = layout.CK_H
+        hdr = np.zeros(layout.CK_HEADER_BYTES, dtype=np.uint8)
+        hdr[H["MAGIC"]: H["MAGIC"] + 8].view(np.uint64)[0] = layout.CK_MAGIC
+        hdr[H["VERSION"]: H["VERSION"] + 16].view(np.int32)[:] = (layout.CK_VERSION, mode, n, layout.ck_words(mode, n))
+        hdr[H["COUNT"]: H["COUNT"] + 8].view(np.int64)[0] = count
+        return hdr
+
+    def records(self) -> np.ndarray:
+        """(count, words) float64 view of the records."""
+        return self._buf[layout.CK_HEADER_BYTES:].view(np.float64).reshape(self.count, self.words)
+
+    def tobytes(self) -> bytes:
+        return self._buf.tobytes()
+
+    @classmethod
+    def frombytes(cls, data) -> "Checkpoint":
+        return cls(data)
+
+    def save(self, path) -> None:
+        with open(path, "wb") as f:
+            f.write(self._buf.data)
+
+    @classmethod
+    def load(cls, path) -> "Checkpoint":
+        with open(path, "rb") as f:
+            return cls(f.read())
+
+    def select(self, indices) -> "Checkpoint":
+        """A new checkpoint of the records `indices`, in that order; an index may repeat (replication)."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.count):
+            raise IndexError(f"checkpoint: record index out of range [0, {self.count})")
+        body = np.ascontiguousarray(self.records()[idx]).view(np.uint8).reshape(-1)
+        return Checkpoint(np.concatenate([self.header(self.mode, self.n, idx.size), body]), copy=False)
+
+    def arrays(self) -> dict:
+        """Views into the records, leading axis the record: state (12n + 18), counter, f_des (n, 3), iters, ipmx
+        (int32; the previous step's ADMM / DD passes and slowest IPM count) and the mode's warm state in the device's
+        agent-major layout -- C-ADMM f (n, n, 3) with f[i] agent i's copy, f_mean (n, 3), lambda_f (n, n, 3); DD
+        lambda_F, lambda_M (n, 3), prev (n, 9) = per agent (f_i, F_i, M_i); centralized prev_f (n, 3)."""
+        rec, n = self.records(), self.n
+        out = {}
+        for arr, (off, words) in layout.ck_fields(self.mode, n).items():
+            name, shape = self._NAMES[arr]
+            out[name] = rec[:, off: off + words].reshape((self.count,) + shape(n))
+        ints = rec.view(np.int32).reshape(self.count, 2 * self.words)
+        for arr, k in layout.CK_INTS.items():
+            out[arr] = ints[:, 2 * layout.ck_ints(n) + k]
+        return out
+
+
 class BatchedController:
     """B independent scenarios of one controller type on one GPU."""
 
@@ -156,6 +254,49 @@ class BatchedController:
         c = np.empty(self.batch, dtype=np.int32)
         L.check(self._lib.dat_get_state(self._h, L.ptr(st), L.ptr(c, L.I)))
         return st, c
+
+    # -- checkpoints (dat_checkpoint_*): scenarios with their controllers' warm state
+    def checkpoint(self, scenarios=None) -> Checkpoint:
+        """The records of `scenarios` (any indices in [0, batch), repeats allowed; None: all, in order)."""
+        if scenarios is None:
+            sc, count = None, self.batch
+        else:
+            sc = L.i32(np.asarray(scenarios).reshape(-1))
+            count = sc.shape[0]
+        nb = ctypes.c_longlong()
+        L.check(self._lib.dat_checkpoint_bytes(self._h, count, ctypes.byref(nb)))
+        buf = np.empty(nb.value, dtype=np.uint8)
+        L.check(self._lib.dat_checkpoint_save(self._h, L.ptr(sc, L.I), count, buf.ctypes.data_as(ctypes.c_void_p),
+                                              nb.value))
+        return Checkpoint(buf, copy=False)
+
+    def restore(self, ckpt, records=None, scenarios=None) -> None:
+        """Write record records[k] of `ckpt` (a Checkpoint, or a blob's bytes) into scenario scenarios[k].  records
+        may repeat (a fork), scenarios must be distinct; None: 0..count-1, count being the length of the list
+        given, else the checkpoint's.  Scenarios not named are untouched; the next closed_loop / control computes
+        desired acceleration and env rows from the restored states, as after set_state.  The blob is checked
+        against the handle first (mode, n, sizes, indices): a DatError names the cause, nothing was written."""
+        data = ckpt._buf if isinstance(ckpt, Checkpoint) else np.frombuffer(bytes(ckpt), dtype=np.uint8)
+        rec = None if records is None else L.i32(np.asarray(records).reshape(-1))
+        sc = None if scenarios is None else L.i32(np.asarray(scenarios).reshape(-1))
+        if rec is not None and sc is not None and rec.shape != sc.shape:
+            raise ValueError(f"restore: {rec.shape[0]} records for {sc.shape[0]} scenarios")
+        if rec is not None or sc is not None:
+            count = (rec if rec is not None else sc).shape[0]
+        elif isinstance(ckpt, Checkpoint):
+            count = ckpt.count
+        else:  # (a raw blob: its own record count, if it has one to read; the library checks the rest)
+            H = layout.CK_H["COUNT"]
+            count = int(data[H: H + 8].view(np.int64)[0]) if data.size >= H + 8 else 0
+            count = min(max(count, 0), self.batch)
+        L.check(self._lib.dat_checkpoint_load(self._h, data.ctypes.data_as(ctypes.c_void_p), data.size,
+                                              L.ptr(rec, L.I), L.ptr(sc, L.I), count))
+
+    def checkpoint_ms(self) -> Tuple[float, float]:
+        """Device time [ms] of the last checkpoint's / restore's (copy kernel, host copy) -- dat_get_checkpoint_ms."""
+        k, c = ctypes.c_double(), ctypes.c_double()
+        L.check(self._lib.dat_get_checkpoint_ms(self._h, ctypes.byref(k), ctypes.byref(c)))
+        return k.value, c.value
 
     # -- steps
     def control(self, states: Optional[np.ndarray] = None, acc_des: Optional[np.ndarray] = None) -> StepResult:
@@ -521,6 +662,10 @@ class _DropIn:
         """Extension (no reference counterpart): IPM stopping tolerance, 1e-8 = Clarabel's default."""
         self._eng.set_qp_tolerance(tol)
 
+    def _warm(self) -> dict:
+        """The scenario's checkpoint record (Checkpoint.arrays of a one-scenario checkpoint), record axis dropped."""
+        return {k: v[0] for k, v in self._eng.checkpoint([0]).arrays().items()}
+
     def get_force_cone_angle_bound(self) -> float:
         return self.max_f_ang
 
@@ -531,9 +676,30 @@ class _DropIn:
 class RQPCentralizedController(_DropIn):
     _mode = L.MODE_CENTRALIZED
 
+    @property
+    def prev_f(self) -> np.ndarray:
+        """(3, n): the solution held on a non-OPTIMAL solve (control/rqp_centralized.py prev_f), read-only."""
+        return self._warm()["prev_f"].T.copy()
+
 
 class RQPCADMMController(_DropIn):
     _mode = L.MODE_CADMM
+
+    # The warm state the reference keeps as attributes (control/rqp_cadmm.py:569-580), read from the device through a
+    # one-scenario checkpoint; read-only (BatchedController.restore writes warm state).
+    @property
+    def f(self) -> np.ndarray:
+        """(3, n, n): f[:, :, i] is agent i's copy."""
+        return self._warm()["f"].transpose(2, 1, 0).copy()
+
+    @property
+    def f_mean(self) -> np.ndarray:
+        return self._warm()["f_mean"].T.copy()
+
+    @property
+    def lambda_f(self) -> np.ndarray:
+        """(3, n, n): lambda_f[:, :, i] is agent i's multiplier."""
+        return self._warm()["lambda_f"].transpose(2, 1, 0).copy()
 
     def set_force_err_tolerance(self, tol: float, use_total_res: bool = True) -> None:
         self._eng.set_force_err_tolerance(tol, use_total_res)
@@ -544,6 +710,28 @@ class RQPCADMMController(_DropIn):
 
 class RQPDDController(_DropIn):
     _mode = L.MODE_DD
+
+    # control/rqp_dd.py:618-632, read from the device through a one-scenario checkpoint; read-only.  f, F, M: the
+    # agents' held solutions (f_i, F_i, M_i), each (3, n) with column i agent i's.
+    @property
+    def f(self) -> np.ndarray:
+        return self._warm()["prev"][:, 0:3].T.copy()
+
+    @property
+    def F(self) -> np.ndarray:
+        return self._warm()["prev"][:, 3:6].T.copy()
+
+    @property
+    def M(self) -> np.ndarray:
+        return self._warm()["prev"][:, 6:9].T.copy()
+
+    @property
+    def lambda_F(self) -> np.ndarray:
+        return self._warm()["lambda_F"].T.copy()
+
+    @property
+    def lambda_M(self) -> np.ndarray:
+        return self._warm()["lambda_M"].T.copy()
 
     def set_force_err_tolerance(self, tol: float) -> None:
         self._eng.set_force_err_tolerance(tol, True)
@@ -694,5 +882,5 @@ class RQPClosedLoop:
         return RQPState.unpack(st[0], self.ctrl.n)
 
 
-__all__ = ["BatchedController", "StepResult", "SolverStatistics", "RQPCentralizedController", "RQPCADMMController",
+__all__ = ["BatchedController", "Checkpoint", "StepResult", "SolverStatistics", "RQPCentralizedController", "RQPCADMMController",
            "RQPDDController", "RQPClosedLoop", "RQPCADMMPrimalSolver", "RQPDDPrimalSolver", "RQPLowLevelController"]

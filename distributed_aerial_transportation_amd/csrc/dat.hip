@@ -28,6 +28,7 @@
 #include <chrono>
 
 #include "../../include/dat.h"
+#include "dat_ckpt.hpp"
 #include "dat_kargs.hpp"
 
 using namespace dat;
@@ -1895,6 +1896,92 @@ __global__ __launch_bounds__(64) void k_agent_qp(KArgs a, AgentQPArgs q) {
   q.cert[k] = (unsigned char)cert;
 }
 
+// ------------------------------------------------------------------------------------------------
+// checkpoint records (dat_checkpoint_save / dat_checkpoint_load; layout: dat_layout.h DAT_CK_*)
+// ------------------------------------------------------------------------------------------------
+// The record's segments as kernel arguments, written from the table of dat_ckpt.hpp (ck_args): the handle's fp64
+// arrays with their words per scenario and record offsets, and the int arrays behind the ints' words (null: the
+// mode has no such array; it reads as 0 and is not written).
+struct CkArgs {
+  int nf, words, ints_off;
+  double* f[CK_MAX_FIELDS];
+  int w[CK_MAX_FIELDS], off[CK_MAX_FIELDS];
+  int* ints[CK_NINTS + 1];
+  int *done, *adv;  // scatter: the closed loop's stamps of the scenarios written (null: the mode has none)
+};
+template <int U>
+struct CkUnit;
+template <>
+struct CkUnit<1> { using T = double; };
+template <>
+struct CkUnit<2> { using T = double2; };
+// the array and the word in it behind word x of scenario sc's record (null: an int word or padding)
+__device__ __forceinline__ double* ck_word(const CkArgs& c, int sc, int x) {
+  for (int k = 0; k < c.nf; ++k) {
+    const int d = x - c.off[k];
+    if ((unsigned)d < (unsigned)c.w[k]) return c.f[k] + (size_t)sc * c.w[k] + d;
+  }
+  return nullptr;
+}
+// One wavefront per record; its lanes walk the record's words in units of U words (U = 2, 16-byte accesses, where
+// every segment's size and offset is even: every source run and every record is then 16-byte aligned; else U = 1),
+// so a wavefront instruction reads and writes runs of up to 1 KiB / 512 B that are contiguous within a segment.
+// k_ckpt_gather: record r of `out` from scenario list[r] (null: r).
+template <int U>
+__global__ __launch_bounds__(256) void k_ckpt_gather(CkArgs c, const int* list, int count, double* out) {
+  using T = typename CkUnit<U>::T;
+  const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+  const long long r = (long long)blockIdx.x * wpb + (threadIdx.x >> 6);
+  if (r < count) {
+    const int sc = list ? list[r] : (int)r;
+    double* rec = out + (size_t)r * c.words;
+    for (int x = lane * U; x < c.words; x += 64 * U) {
+      double v[2] = {0.0, 0.0};
+      if ((unsigned)(x - c.ints_off) < (unsigned)CK_INT_WORDS) {
+        for (int j = 0; j < U; ++j) {
+          const int i0 = 2 * (x + j - c.ints_off);
+          v[j] = __hiloint2double(c.ints[i0 + 1] ? c.ints[i0 + 1][sc] : 0, c.ints[i0] ? c.ints[i0][sc] : 0);
+        }
+      } else if (const double* p = ck_word(c, sc, x)) {
+        const T t = *(const T*)p;
+        memcpy(v, &t, sizeof(T));
+      }
+      T t;
+      memcpy(&t, v, sizeof(T));
+      *(T*)(rec + x) = t;
+    }
+  }
+}
+// k_ckpt_scatter: record rec[r] - base (null: r - base) of `in` into scenario scen[r] (null: r); the scenarios are
+// distinct.  Their stamps are cleared: 0 is no step's stamp (next_serial).
+template <int U>
+__global__ __launch_bounds__(256) void k_ckpt_scatter(CkArgs c, const double* in, const int* recs, const int* scen,
+                                                      int base, int count) {
+  using T = typename CkUnit<U>::T;
+  const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+  const long long r = (long long)blockIdx.x * wpb + (threadIdx.x >> 6);
+  if (r < count) {
+    const int sc = scen ? scen[r] : (int)r;
+    const double* rec = in + (size_t)((recs ? recs[r] : (int)r) - base) * c.words;
+    for (int x = lane * U; x < c.words; x += 64 * U) {
+      const T t = *(const T*)(rec + x);
+      double v[2] = {0.0, 0.0};
+      memcpy(v, &t, sizeof(T));
+      if ((unsigned)(x - c.ints_off) < (unsigned)CK_INT_WORDS) {
+        for (int j = 0; j < U; ++j) {
+          const int i0 = 2 * (x + j - c.ints_off);
+          if (c.ints[i0]) c.ints[i0][sc] = __double2loint(v[j]);
+          if (c.ints[i0 + 1]) c.ints[i0 + 1][sc] = __double2hiint(v[j]);
+        }
+      } else if (double* p = ck_word(c, sc, x)) {
+        *(T*)p = t;
+      }
+    }
+    if (lane == 0 && c.done) c.done[sc] = 0;
+    if (lane == 0 && c.adv) c.adv[sc] = 0;
+  }
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1996,6 +2083,11 @@ struct dat_handle {
   int* pipe_lists = nullptr;  // slist and rlist of the two pipeline streams' drains (4 x B; the handle's stream: slist, rlist)
   double agent_qp_ms = 0.0;  // device time of the last dat_solve_agent_qp_batch launch
   int ll_kind = 0;  // LL_PD (example/rqp_example.py:113) or LL_SM
+  // dat_checkpoint_save / _load: the records' staging buffer and the index lists, grown on demand
+  double* ck_stage = nullptr;
+  int* ck_list = nullptr;
+  size_t ck_stage_cap = 0, ck_list_cap = 0;
+  double ck_kernel_ms = 0.0, ck_copy_ms = 0.0;  // device time of the last save's / load's copy kernel and host copy
   // what the handle owns: dat_destroy frees by list
   std::vector<void*> allocs;
   std::vector<hipStream_t> streams;
@@ -2631,6 +2723,64 @@ int read_words(dat_handle* h, const unsigned long long* src, std::initializer_li
   return 0;
 }
 
+// ---- checkpoints ---------------------------------------------------------------------------------------------
+// the handle's record as the copy kernels' arguments: the table of dat_ckpt.hpp with the handle's arrays put in
+CkArgs ck_args(const dat_handle* h) {
+  CkArgs c;
+  memset(&c, 0, sizeof(c));
+  const int n = h->cfg.n;
+#define DAT_CK_X(arr, w_, o_) \
+  c.f[c.nf] = h->arr;         \
+  c.w[c.nf] = (w_);           \
+  c.off[c.nf] = (o_);         \
+  ++c.nf;
+  DAT_CK_FIELDS_OF(h->cfg.mode, DAT_CK_X, n);
+#undef DAT_CK_X
+#define DAT_CK_X(arr, k) c.ints[k] = h->arr;
+  DAT_CK_INT_FIELDS(DAT_CK_X)
+#undef DAT_CK_X
+  c.ints_off = DAT_CK_INTS(n);
+  c.words = ck_record_words(h->cfg.mode, n);
+  c.done = h->done;
+  c.adv = h->adv;
+  return c;
+}
+// 16-byte units where every segment's words and offset are even (kernels: CkUnit)
+bool ck_wide(const CkArgs& c) {
+  bool even = c.ints_off % 2 == 0 && c.words % 2 == 0;
+  for (int k = 0; k < c.nf; ++k) even = even && c.w[k] % 2 == 0 && c.off[k] % 2 == 0;
+  return even;
+}
+int ck_blocks(int count) { return (int)(((long long)count + 3) / 4); }  // (four wavefronts, one record each, per block)
+
+// the spans of a save / load (events of the handle's, recorded on its stream and reached): its kernel, its host copy
+int ck_times(dat_handle* h, hipEvent_t k0, hipEvent_t k1, hipEvent_t c0, hipEvent_t c1) {
+  float km = 0.f, cm = 0.f;
+  HIPCHK(hipEventElapsedTime(&km, k0, k1));
+  HIPCHK(hipEventElapsedTime(&cm, c0, c1));
+  h->ck_kernel_ms = km;
+  h->ck_copy_ms = cm;
+  return 0;
+}
+
+// A buffer of the handle's grown to `need` elements (not cleared: every word read was written before).  A failure
+// leaves the old buffer in place.
+template <class T>
+int ck_grow(dat_handle* h, T** p, size_t* cap, size_t need) {
+  if (need <= *cap) return 0;
+  void* q = nullptr;
+  const hipError_t e = hipMalloc(&q, need * sizeof(T));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(std::string("checkpoint staging buffer: ") + hipGetErrorString(e));
+  }
+  dfree(h, *p);
+  h->allocs.push_back(q);
+  *p = (T*)q;
+  *cap = need;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2948,6 +3098,85 @@ int dat_get_state(dat_handle* h, double* state, int* counters) {
   if (counters)
     HIPCHK(hipMemcpyAsync(counters, h->counter, sizeof(int) * h->cfg.batch, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dat_checkpoint_bytes(dat_handle* h, int count, long long* bytes) {
+  if (!h || !bytes) return fail("dat_checkpoint_bytes: null argument");
+  if (count < 0) return fail("dat_checkpoint_bytes: negative count " + std::to_string(count));
+  *bytes = ck_blob_bytes(h->cfg.mode, h->cfg.n, count);
+  return 0;
+}
+
+int dat_checkpoint_save(dat_handle* h, const int* scenarios, int count, void* blob, long long bytes) {
+  if (!h) return fail("dat_checkpoint_save: null handle");
+  std::string m;
+  if (ck_check_save(h->cfg.mode, h->cfg.n, h->cfg.batch, scenarios, count, blob, bytes, &m)) return fail(m);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipStream_t s : h->streams) HIPCHK(hipStreamSynchronize(s));
+  ck_put_header(blob, h->cfg.mode, h->cfg.n, count);
+  if (count == 0) return 0;
+  const CkArgs c = ck_args(h);
+  const size_t words = (size_t)count * c.words;
+  if (ck_grow(h, &h->ck_stage, &h->ck_stage_cap, words)) return -1;
+  if (scenarios) {
+    if (ck_grow(h, &h->ck_list, &h->ck_list_cap, (size_t)count)) return -1;
+    HIPCHK(hipMemcpyAsync(h->ck_list, scenarios, sizeof(int) * count, hipMemcpyHostToDevice, h->stream));
+  }
+  const int* list = scenarios ? h->ck_list : nullptr;
+  HIPCHK(hipEventRecord(h->e0, h->stream));
+  hipLaunchKernelGGL(ck_wide(c) ? k_ckpt_gather<2> : k_ckpt_gather<1>, dim3(ck_blocks(count)), dim3(256), 0, h->stream, c,
+                     list, count, h->ck_stage);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ek, h->stream));
+  HIPCHK(hipMemcpyAsync((char*)blob + DAT_CK_HEADER_BYTES, h->ck_stage, sizeof(double) * words, hipMemcpyDeviceToHost,
+                        h->stream));
+  HIPCHK(hipEventRecord(h->e1, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return ck_times(h, h->e0, h->ek, h->ek, h->e1);
+}
+
+int dat_checkpoint_load(dat_handle* h, const void* blob, long long bytes, const int* records, const int* scenarios,
+                        int count) {
+  if (!h) return fail("dat_checkpoint_load: null handle");
+  std::string m;
+  long long lo = 0, hi = 0;
+  if (ck_check_load(h->cfg.mode, h->cfg.n, h->cfg.batch, blob, bytes, records, scenarios, count, &lo, &hi, &m))
+    return fail(m);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipStream_t s : h->streams) HIPCHK(hipStreamSynchronize(s));
+  const CkArgs c = ck_args(h);
+  // the records named lie in [lo, hi) of the blob: that stretch is uploaded, once
+  const size_t words = (size_t)(hi - lo) * c.words;
+  if (ck_grow(h, &h->ck_stage, &h->ck_stage_cap, words) || ck_grow(h, &h->ck_list, &h->ck_list_cap, (size_t)2 * count))
+    return -1;
+  const hipStream_t st = h->stream;
+  HIPCHK(hipEventRecord(h->e0, st));
+  HIPCHK(hipMemcpyAsync(h->ck_stage, (const char*)blob + DAT_CK_HEADER_BYTES + sizeof(double) * (size_t)lo * c.words,
+                        sizeof(double) * words, hipMemcpyHostToDevice, st));
+  int *recs = nullptr, *scen = nullptr;
+  if (records) {
+    recs = h->ck_list;
+    HIPCHK(hipMemcpyAsync(recs, records, sizeof(int) * count, hipMemcpyHostToDevice, st));
+  }
+  if (scenarios) {
+    scen = h->ck_list + count;
+    HIPCHK(hipMemcpyAsync(scen, scenarios, sizeof(int) * count, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipEventRecord(h->ek, st));
+  hipLaunchKernelGGL(ck_wide(c) ? k_ckpt_scatter<2> : k_ckpt_scatter<1>, dim3(ck_blocks(count)), dim3(256), 0, st, c,
+                     (const double*)h->ck_stage, (const int*)recs, (const int*)scen, (int)lo, count);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->e1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ck_times(h, h->ek, h->e1, h->e0, h->ek);
+}
+
+int dat_get_checkpoint_ms(dat_handle* h, double* kernel_ms, double* copy_ms) {
+  if (!h) return fail("dat_get_checkpoint_ms: null handle");
+  if (kernel_ms) *kernel_ms = h->ck_kernel_ms;
+  if (copy_ms) *copy_ms = h->ck_copy_ms;
   return 0;
 }
 

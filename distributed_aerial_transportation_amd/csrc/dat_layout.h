@@ -73,6 +73,45 @@
 #define DAT_LOG_ST_XERR(n) (4 * (n) + DAT_STATE_SIZE(n))
 #define DAT_LOG_ST_WORDS(n) (4 * (n) + DAT_STATE_SIZE(n) + 2)
 
+// ---- checkpoint record (dat_checkpoint_*), in 8-byte words ------------------------------------------------------
+// One record: everything of one scenario that a later step's arithmetic reads.  All modes: the state block, f_des
+// (3n, agent-major: the forces the rollout applies), then 32-bit ints packed two per word: int[0] the polar counter,
+// int[1] iters and int[2] ipmx (the previous step's ADMM / DD pass count and slowest IPM count: k_cadmm's IPM start
+// regime, the drain order and the tail rule read them), int[3] zero.  Then the mode's warm state, in the device's
+// agent-major layout: C-ADMM f (n x 3n, agent i's copy at 3n i), f_mean (3n), lambda_f (n x 3n); DD lambda_F,
+// lambda_M (3n each), prev (9n: per agent f_i, F_i, M_i); centralized prev_f (3n).  A record is padded to an even
+// number of words, so every record of a blob starts 16-byte aligned behind the header.
+#define DAT_CK_STATE(n) 0
+#define DAT_CK_FDES(n) (DAT_STATE_SIZE(n))
+#define DAT_CK_INTS(n) (DAT_STATE_SIZE(n) + 3 * (n))  // int[0] counter, int[1] iters, int[2] ipmx, int[3] zero
+#define DAT_CK_WARM(n) (DAT_STATE_SIZE(n) + 3 * (n) + 2)
+#define DAT_CK_F(n) (DAT_CK_WARM(n))                               // C-ADMM
+#define DAT_CK_FMEAN(n) (DAT_CK_WARM(n) + 3 * (n) * (n))
+#define DAT_CK_LAMF(n) (DAT_CK_WARM(n) + 3 * (n) * (n) + 3 * (n))
+#define DAT_CK_END_CADMM(n) (DAT_CK_WARM(n) + 6 * (n) * (n) + 3 * (n))
+#define DAT_CK_LAMF_DD(n) (DAT_CK_WARM(n))                         // DD
+#define DAT_CK_LAMM_DD(n) (DAT_CK_WARM(n) + 3 * (n))
+#define DAT_CK_PREV_DD(n) (DAT_CK_WARM(n) + 6 * (n))
+#define DAT_CK_END_DD(n) (DAT_CK_WARM(n) + 15 * (n))
+#define DAT_CK_PREVF(n) (DAT_CK_WARM(n))                           // centralized
+#define DAT_CK_END_CENT(n) (DAT_CK_WARM(n) + 3 * (n))
+#define DAT_CK_WORDS_CADMM(n) (DAT_CK_END_CADMM(n) + (DAT_CK_END_CADMM(n) & 1))
+#define DAT_CK_WORDS_DD(n) (DAT_CK_END_DD(n) + (DAT_CK_END_DD(n) & 1))
+#define DAT_CK_WORDS_CENT(n) (DAT_CK_END_CENT(n) + (DAT_CK_END_CENT(n) & 1))
+// The blob: a header of DAT_CK_HEADER_BYTES, then the records back to back.  Header fields at byte offsets
+// (little-endian): magic (8, "DATCKPT\0"), format version, mode (DAT_MODE_*), n, words per record (4 each), record
+// count (8), zeros to the header's end.
+#define DAT_CK_HEADER_BYTES 64
+#define DAT_CK_MAGIC 0x0054504B43544144
+#define DAT_CK_VERSION 1
+#define DAT_CK_H_MAGIC 0
+#define DAT_CK_H_VERSION 8
+#define DAT_CK_H_MODE 12
+#define DAT_CK_H_N 16
+#define DAT_CK_H_WORDS 20
+#define DAT_CK_H_COUNT 24
+#define DAT_CK_H_PAD 32
+
 #define DAT_BARK_RADIUS 0.3
 #define DAT_BARK_HALF_HEIGHT 2.0
 #define DAT_NENV 10            // env CBF rows per QP (control/rqp_cadmm.py:218)

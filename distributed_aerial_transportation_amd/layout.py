@@ -55,3 +55,36 @@ def p_off(name: str, n: int) -> int:
 
 def s_off(name: str, n: int) -> int:
     return fn("DAT_S_" + name, n)
+
+
+# ---- checkpoint record (DAT_CK_*) and its field table (csrc/dat_ckpt.hpp, the lists the copy kernels are written from)
+CK_HEADER_BYTES = const("DAT_CK_HEADER_BYTES")
+CK_MAGIC = const("DAT_CK_MAGIC")
+CK_VERSION = const("DAT_CK_VERSION")
+CK_H = {k[len("DAT_CK_H_"):]: const(k) for k in _const if k.startswith("DAT_CK_H_")}  # header fields' byte offsets
+CK_MODES = {0: "CENT", 1: "CADMM", 2: "DD"}  # DAT_MODE_* -> the macros' suffix
+CK_INTS = {}  # int array of the handle -> index among the ints at DAT_CK_INTS(n)
+_ck_lists: dict = {}  # list suffix (ALL, CADMM, DD, CENT) -> [(array of the handle, words expression, offset macro)]
+with open(os.path.join(os.path.dirname(_HDR), "dat_ckpt.hpp")) as _f:
+    _src = _f.read().replace("\\\n", " ")
+for _m in re.finditer(r"#define\s+DAT_CK_FIELDS_(\w+)\(X, n\)(.*)", _src):
+    _ck_lists[_m.group(1)] = re.findall(r"X\((\w+),\s*(.+?),\s*(DAT_CK_\w+)\(n\)\)", _m.group(2))
+for _m in re.finditer(r"X\((\w+), (\d)\)", re.search(r"#define\s+DAT_CK_INT_FIELDS\(X\)(.*)", _src).group(1)):
+    CK_INTS[_m.group(1)] = int(_m.group(2))
+
+
+def ck_words(mode: int, n: int) -> int:
+    """Words (8 bytes) of one checkpoint record of `mode` (DAT_MODE_*) at team size n."""
+    return fn("DAT_CK_WORDS_" + CK_MODES[mode], n)
+
+
+def ck_ints(n: int) -> int:
+    return fn("DAT_CK_INTS", n)
+
+
+def ck_fields(mode: int, n: int) -> dict:
+    """The fp64 arrays of a record: array of the handle -> (record offset, words), from the table of dat_ckpt.hpp."""
+    out = {}
+    for arr, words, off in _ck_lists["ALL"] + _ck_lists[CK_MODES[mode]]:
+        out[arr] = (fn(off, n), int(_eval(words, {"n": n})))
+    return out

@@ -96,6 +96,42 @@ int dat_reset_warm_start(dat_handle* h);
 int dat_set_state(dat_handle* h, const double* state /* B x DAT_STATE_SIZE(n) */, const int* counters /* B or NULL */);
 int dat_get_state(dat_handle* h, double* state, int* counters);
 
+/* ---- checkpoints: scenarios with their controllers' warm state ------------------------------------------------
+ * dat_set_state / dat_get_state move the rigid-body state and the polar counter; a scenario's next control step
+ * also reads what the reference keeps in its controller objects between calls -- C-ADMM f, f_mean, lambda_f
+ * (control/rqp_cadmm.py:569-580), DD lambda_F, lambda_M and the agents' previous (f_i, F_i, M_i)
+ * (control/rqp_dd.py:618-632), the centralized prev_f -- and, with no reference counterpart, the forces the rollout
+ * applies (f_des) and the previous step's pass count and slowest IPM count, from which the kernels take the IPM
+ * start regime, the drain order and the tail rule.  A checkpoint record is all of that for one scenario
+ * (csrc/dat_layout.h, DAT_CK_*); a blob is a header of DAT_CK_HEADER_BYTES and `count` records.  Parameters,
+ * forests, tolerances, schedule switches, work counters, the log and a step's outputs (qp_status, min_env_dist,
+ * collision, err_seq) are not part of it.  A scenario's arithmetic depends on neither its batch, its slot nor the
+ * schedule, so a record restored into any slot of any handle of the same mode and n (with the same parameters,
+ * forest and settings) continues bitwise as the scenario it was taken from.
+ *
+ * dat_checkpoint_bytes: the size of a blob of `count` records of this handle.
+ * dat_checkpoint_save: record k from scenario scenarios[k], any indices in [0, B), repeats allowed (NULL with
+ * count = B: all, in order); `bytes` is the blob's size as dat_checkpoint_bytes gives it.  Waits for every stream of
+ * the handle, gathers the records on the device and copies them out in one piece.
+ * dat_checkpoint_load: blob record records[k] into scenario scenarios[k], k < count.  records may repeat (one
+ * record into many scenarios is a fork; the blob's stretch that holds the records named is uploaded once; NULL:
+ * 0..count-1); scenarios must be distinct (NULL: 0..count-1); scenarios not named are untouched.  Needs no
+ * parameters, touches neither the log nor its clock, and is legal wherever dat_set_state is.  The blob is checked
+ * on the host before anything is launched or copied -- magic, version, mode, n and words per record against the
+ * handle, `bytes` against the header's record count, every index, duplicate destinations -- and every failure
+ * returns < 0 with a message that names the cause and leaves the handle as it was.  As after dat_set_state, the
+ * next dat_closed_loop / dat_control_step computes desired acceleration and env rows from the state; the loaded
+ * scenarios' advance stamps are cleared, so they are never taken for the coming step's.  Until that step
+ * dat_debug_get_env_class still reports what the handle held before the load. */
+int dat_checkpoint_bytes(dat_handle* h, int count, long long* bytes);
+int dat_checkpoint_save(dat_handle* h, const int* scenarios, int count, void* blob, long long bytes);
+int dat_checkpoint_load(dat_handle* h, const void* blob, long long bytes, const int* records, const int* scenarios,
+                        int count);
+/* Device time [ms] of the last dat_checkpoint_save / dat_checkpoint_load that copied records (HIP events on the
+ * handle's stream): of its gather / scatter kernel, and of its copy between the staging buffer and the blob (a
+ * load's includes the index lists).  Either pointer may be NULL. */
+int dat_get_checkpoint_ms(dat_handle* h, double* kernel_ms, double* copy_ms);
+
 /* ---- one high-level control step for every scenario ---------------------------------------
  * Replaces controller.control(state, acc_des) -> (f_des, SolverStatistics):
  *   RQPCADMMController.control   control/rqp_cadmm.py:631-675  (agent solves :482-501)
