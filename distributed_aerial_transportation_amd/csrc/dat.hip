@@ -607,7 +607,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
       if (vi == 0)
         for (int c = 0; c < 3; ++c) fb[3 * i + c] = a.cfbar[(size_t)sc * N3 + 3 * i + c];
       // (the tail: the lane's record in LDS, behind the env image -- a generic pointer, flat loads go to LDS)
-      bst = RB ? L.env + env_lds_doubles(NE) + i * best_size(1) : a.best + ((size_t)sc * n + i) * best_rec(1);
+      bst = RB ? L.env + env_lds_doubles(NE) + i * best_size(1) : a.best + ((size_t)sc * n + i) * BEST_REC;
       iter = 0;
       prev_iter = a.iters[sc];  // the previous step's ADMM iterations (rewritten when the scenario stops)
       qstat = ST_OPTIMAL;
@@ -974,6 +974,21 @@ __host__ __device__ inline int dd_setup_hs(int n) {
   if (n <= DD_REG_NMAX) return 171 * n + 1 + 2 * N;  // k_dd_setup<n>
   return 2 * N * N > 171 * n + 1 ? 2 * N * N : 171 * n + 1;
 }
+// dynamic LDS of a k_dd_setup workgroup: the kernel's regions in order and their end.  The kernel carves its smem;
+// the host carves from a null base and reads the launch's bytes, so the layout is stated once.
+struct DdSetupLds {
+  double *Qi, *Rts, *H, *fac, *end;
+  size_t bytes() const { return (size_t)((char*)end - (char*)Qi); }
+};
+__host__ __device__ inline DdSetupLds dd_setup_carve(double* smem, int n) {
+  DdSetupLds L;
+  L.Qi = smem;                       // n x 81   sym(Q_i^-1)
+  L.Rts = L.Qi + 81 * n;             // n x 9
+  L.H = L.Rts + 9 * n;               // N x 2N   [H | I]
+  L.fac = L.H + dd_setup_hs(n);      // N
+  L.end = L.fac + 6 * n;
+  return L;
+}
 
 // H = A blkdiag(Q_j^-1) A' (control/rqp_dd.py:642-655) and H^-1 by Gauss-Jordan on [H | I], n = NB,
 // with the columns of [H | I] in registers: lane c owns column c and, when 2N > 64, column c + 64 (an
@@ -1083,16 +1098,13 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
   const int sc = blockIdx.x;
   const int lane = threadIdx.x;
   if (sc >= a.B) return;
-  double* Qi = smem;              // n x 81   sym(Q_i^-1)
-  double* Rts = Qi + 81 * n;      // n x 9
-  double* H = Rts + 9 * n;        // N x 2N   [H | I]
-  double* fac = H + dd_setup_hs(n);  // N
+  const DdSetupLds L = dd_setup_carve(smem, n);
   const double* prm = prm_of(a, sc);
   const double* st = a.state + (size_t)sc * a.S;
   // Q_i^-1 by Gauss-Jordan with partial pivoting (np.linalg.inv) on [Q_i | I] in LDS, spread over
   // the wavefront: lane pairs (agent j, column c) update one column each, with the per-element
   // arithmetic of the serial elimination (pivot column copied before the update).
-  double* Aug = H;                         // n x 9 x 18, in the [H | I] area (built afterwards)
+  double* Aug = L.H;                       // n x 9 x 18, in the [H | I] area (built afterwards)
   double* colk = Aug + 162 * n;            // n x 9: column k before step k's update
   int* pivr = (int*)(colk + 9 * n);        // n
   if (lane < n) {
@@ -1100,7 +1112,7 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
     dd_strong_convexity(prm, n, st, lane, Q);
     for (int r = 0; r < 9; ++r)
       for (int c = 0; c < 18; ++c) Aug[162 * lane + 18 * r + c] = c < 9 ? Q[9 * r + c] : (c - 9 == r ? 1.0 : 0.0);
-    make_Rt(prm + DAT_P_RCOM(n) + 3 * lane, st + DAT_S_RL(n), Rts + 9 * lane);
+    make_Rt(prm + DAT_P_RCOM(n) + 3 * lane, st + DAT_S_RL(n), L.Rts + 9 * lane);
   }
   __syncthreads();
   for (int k = 0; k < 9; ++k) {
@@ -1137,11 +1149,11 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
   for (int e = lane; e < 81 * n; e += 64) {
     const int j = e / 81, rc = e - 81 * j, r = rc / 9, c = rc - 9 * r;
     const double* A = Aug + 162 * j;
-    Qi[e] = 0.5 * (A[18 * r + 9 + c] + A[18 * c + 9 + r]);
+    L.Qi[e] = 0.5 * (A[18 * r + 9 + c] + A[18 * c + 9 + r]);
   }
   __syncthreads();
   if constexpr (NB > 0) {
-    dd_setup_h_regs<NB>(a, sc, Qi, Rts, H + 171 * n + 1);  // pivot columns past the Q_i elimination area
+    dd_setup_h_regs<NB>(a, sc, L.Qi, L.Rts, L.H + 171 * n + 1);  // pivot columns past the Q_i elimination area
     return;
   }
   // H = A blkdiag(Q_j^-1) A'  (control/rqp_dd.py:642-655); row r of A restricted to block j:
@@ -1149,7 +1161,7 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
   // every index below is compile-time after unrolling, so v stays in registers (no scratch)
   auto arow = [&](int r, int j, double* v) {
     const int ag = r / 6, comp = r % 6;
-    const double* rt = Rts + 9 * j + 3 * (comp >= 3 ? comp - 3 : 0);
+    const double* rt = L.Rts + 9 * j + 3 * (comp >= 3 ? comp - 3 : 0);
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
       double x = 0.0;
@@ -1166,7 +1178,7 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
       double vr[9], vc[9];
       arow(r, j, vr);
       arow(c, j, vc);
-      const double* Q = Qi + 81 * j;
+      const double* Q = L.Qi + 81 * j;
 #pragma unroll
       for (int p = 0; p < 9; ++p) {
         if (vr[p] == 0.0) continue;
@@ -1176,27 +1188,27 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
         s += vr[p] * t;
       }
     }
-    H[2 * N * r + c] = s;
-    H[2 * N * r + N + c] = (r == c) ? 1.0 : 0.0;
+    L.H[2 * N * r + c] = s;
+    L.H[2 * N * r + N + c] = (r == c) ? 1.0 : 0.0;
   }
   __syncthreads();
   // Gauss-Jordan on [H | I] (H is SPD: no pivoting needed)
   // Each lane owns whole columns of [H | I] (no index division; a row of the tile is contiguous
   // across lanes, so the LDS accesses are conflict-free); per-element operation order as before.
   for (int k = 0; k < N; ++k) {
-    double piv = H[2 * N * k + k];
-    for (int r = lane; r < N; r += 64) fac[r] = H[2 * N * r + k];
+    double piv = L.H[2 * N * k + k];
+    for (int r = lane; r < N; r += 64) L.fac[r] = L.H[2 * N * r + k];
     __syncthreads();
     for (int c = lane; c < 2 * N; c += 64) {
-      const double hk = H[2 * N * k + c] / piv;
-      H[2 * N * k + c] = hk;
+      const double hk = L.H[2 * N * k + c] / piv;
+      L.H[2 * N * k + c] = hk;
       for (int r = 0; r < N; ++r)
-        if (r != k) H[2 * N * r + c] -= fac[r] * hk;
+        if (r != k) L.H[2 * N * r + c] -= L.fac[r] * hk;
     }
     __syncthreads();
   }
   double* out = a.dHinv + (size_t)sc * N * N;
-  for (int e = lane; e < N * N; e += 64) out[e] = H[2 * N * (e / N) + N + (e % N)];
+  for (int e = lane; e < N * N; e += 64) out[e] = L.H[2 * N * (e / N) + N + (e % N)];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1208,6 +1220,31 @@ constexpr int DD_ES = 7, DD_RS = 5;
 // 23.8 -> 22.7 ms).  The 3 base rows' IPM state stays in registers: RowLds measured 26.2 ms, and rows
 // (+ aux slots) in LDS without a forest measured no gain on C3 in round 3 (git history).
 __host__ __device__ constexpr int dd_area_doubles(bool env) { return env ? ENV_LDS_DOUBLES : 0; }
+constexpr int DD_SLOT_INTS = 64;  // ints of each per-slot array of k_dd (G <= 21 used)
+// dynamic LDS of a k_dd workgroup of G = floor(64/n) scenario slots (NT = G n lanes): as DdSetupLds
+struct DdLds {
+  double *X, *lamF, *lamM, *E, *Rts, *red, *envs;
+  QPShared* shs;
+  int *sid, *done, *wmx, *end;
+  size_t bytes() const { return (size_t)((char*)end - (char*)X); }
+};
+__host__ __device__ inline DdLds dd_carve(double* smem, int n, bool env) {
+  const int N3 = 3 * n, G = 64 / n, NT = G * n;
+  DdLds L;
+  L.X = smem;                                       // NT x 9   (f_i, F_i, M_i)
+  L.lamF = L.X + al2(NT * 9);                       // G x 3n
+  L.lamM = L.lamF + al2(G * N3);                    // G x 3n
+  L.E = L.lamM + al2(G * N3);                       // NT x ES  consensus error (ES = 7: odd stride, no bank conflicts)
+  L.Rts = L.E + al2(NT * DD_ES);                    // G x n x RT_STRIDE
+  L.red = L.Rts + G * RT_STRIDE * n;                // 64 x DD_RS
+  L.shs = (QPShared*)(L.red + 64 * DD_RS);          // G
+  L.envs = (double*)(L.shs + G);                    // EnvLds image (env only)
+  L.sid = (int*)(L.envs + dd_area_doubles(env));    // G: scenario of the slot (-1 empty, -2 retired)
+  L.done = L.sid + DD_SLOT_INTS;                    // G: the slot's scenario stopped in this pass
+  L.wmx = L.done + DD_SLOT_INTS;                    // G: IPM iterations of the slot's slowest agent QP this step
+  L.end = L.wmx + DD_SLOT_INTS;
+  return L;
+}
 // k_dd_key: drain-order key of every scenario -- the previous step's (DD iteration count, slowest agent
 // QP's IPM iterations), longest first, as k_cadmm's key -- sorted by k_bucket into one queue (class 0).
 // DD agent QPs run the conservative IPM start (9-10 iterations on average): bins <= 8, 9-10, 11-13, >= 14.
@@ -1231,27 +1268,17 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
   const int lane = threadIdx.x;
   const int ls = lane / n, i = lane - ls * n;
   const int lsc = ls < G ? ls : 0;
-  double* X = smem;                     // NT x 9   (f_i, F_i, M_i)
-  double* lamF = X + al2(NT * 9);       // G x 3n
-  double* lamM = lamF + al2(G * N3);    // G x 3n
-  double* E = lamM + al2(G * N3);       // NT x ES  consensus error (ES = 7: odd stride, no bank conflicts)
-  double* Rts = E + al2(NT * DD_ES);    // G x n x RT_STRIDE
-  double* red = Rts + G * RT_STRIDE * n;  // 64 x DD_RS
-  QPShared* shs = (QPShared*)(red + 64 * DD_RS);  // G
-  double* envs = (double*)(shs + G);              // EnvLds image (ENV only)
-  int* sid = (int*)(envs + dd_area_doubles(ENV));  // G: scenario of the slot (-1 empty, -2 retired)
-  int* done = sid + 64;                           // G: the slot's scenario stopped in this pass
-  int* wmx = done + 64;                           // G: IPM iterations of the slot's slowest agent QP this step
-  QPShared& S = shs[lsc];
-  double* myX = X + lane * 9;
-  double* lF = lamF + lsc * N3;
-  double* lM = lamM + lsc * N3;
-  double* rts = Rts + lsc * RT_STRIDE * n;
+  const DdLds L = dd_carve(smem, n, ENV);
+  QPShared& S = L.shs[lsc];
+  double* myX = L.X + lane * 9;
+  double* lF = L.lamF + lsc * N3;
+  double* lM = L.lamM + lsc * N3;
+  double* rts = L.Rts + lsc * RT_STRIDE * n;
   const int cnt = a.scount[sc_at(SC_SIZE, 0)], first = a.scount[sc_at(SC_START, 0)];
-  const LdsRef<QPShared> shr{shs, lsc};
-  const EnvLds err{envs, lane};
-  const RtLds rtr{Rts, (lsc * n + i) * RT_STRIDE};
-  if (lane < G) sid[lane] = -1;
+  const LdsRef<QPShared> shr{L.shs, lsc};
+  const EnvLds err{L.envs, lane};
+  const RtLds rtr{L.Rts, (lsc * n + i) * RT_STRIDE};
+  if (lane < G) L.sid[lane] = -1;
   __syncthreads();
 
   QPLane<1> P;
@@ -1270,14 +1297,14 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
   for (;;) {
     DAT_PHASE(11);
     // ---- refill empty slots from the queue
-    if (lane < NT && i == 0 && sid[ls] == -1) {
+    if (lane < NT && i == 0 && L.sid[ls] == -1) {
       const int q = atomicAdd(a.scount + sc_at(SC_HEAD, 0), 1);
-      sid[ls] = q < cnt ? a.slist[first + q] : -2;
-      done[ls] = 0;
-      wmx[ls] = 0;
+      L.sid[ls] = q < cnt ? a.slist[first + q] : -2;
+      L.done[ls] = 0;
+      L.wmx[ls] = 0;
     }
     __syncthreads();
-    const int slot_sc = lane < NT ? sid[ls] : -2;
+    const int slot_sc = lane < NT ? L.sid[ls] : -2;
     const bool fresh = slot_sc >= 0 && slot_sc != sc;
     if (fresh) {
       sc = slot_sc;
@@ -1291,7 +1318,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       }
       for (int c = 0; c < 9; ++c) prev[c] = a.dprev[((size_t)sc * n + i) * 9 + c];
       for (int c = 0; c < 9; ++c) myX[c] = prev[c];  // the controller's current (f, F, M)
-      bst = a.best + ((size_t)sc * n + i) * best_rec(1);
+      bst = a.best + ((size_t)sc * n + i) * BEST_REC;
 #if DAT_DD_WARM
       wrl = a.wrec + ((size_t)sc * n + i) * WREC_SIZE;
       wrl[0] = 0.0;
@@ -1317,7 +1344,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
         mdist = env.min_env_dist;
         EnvRows Ev;
         set_env_rows(P, Ev, S, emask, lhs, rhs);
-        env_to_lds(envs, lane, Ev);
+        env_to_lds(L.envs, lane, Ev);
       }
     }
     const bool active = slot_sc >= 0;
@@ -1366,7 +1393,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       wc.loose += inband_loose(o);
       wc.refs += o.refs;
       wc.corrs += o.corrs;
-      atomicMax(&wmx[ls], o.iters);
+      atomicMax(&L.wmx[ls], o.iters);
 #ifdef DAT_ITER_HIST
       atomicAdd(&g_iter_hist[o.iters < 63 ? o.iters : 63], 1ull);
 #endif
@@ -1383,7 +1410,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
         const double* feq = prm + DAT_P_FEQ(n);
         double s3[3] = {0, 0, 0};
         for (int k = 0; k < n; ++k)
-          for (int c = 0; c < 3; ++c) s3[c] += (i == 0) ? X[(ls * n + k) * 9 + c] : feq[3 * k + c];
+          for (int c = 0; c < 3; ++c) s3[c] += (i == 0) ? L.X[(ls * n + k) * 9 + c] : feq[3 * k + c];
         dd_fallback(prm, n, i, s3, prev);
       }
     }
@@ -1399,33 +1426,33 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       double sf[3] = {0, 0, 0}, sm[3] = {0, 0, 0};
       for (int k = 0; k < n; ++k) {
         if (k == i) continue;
-        const double* fk = X + (ls * n + k) * 9;
+        const double* fk = L.X + (ls * n + k) * 9;
         double m3[3];
         mv3(rts + RT_STRIDE * k, fk, m3);
         for (int c = 0; c < 3; ++c) { sf[c] += fk[c]; sm[c] += m3[c]; }
       }
       for (int c = 0; c < 3; ++c) {
-        E[lane * DD_ES + c] = myX[3 + c] - sf[c];
-        E[lane * DD_ES + 3 + c] = myX[6 + c] - sm[c];
+        L.E[lane * DD_ES + c] = myX[3 + c] - sf[c];
+        L.E[lane * DD_ES + 3 + c] = myX[6 + c] - sm[c];
       }
-      red[lane * DD_RS + 0] = col ? 1.0 : 0.0;
-      red[lane * DD_RS + 1] = mdist;
+      L.red[lane * DD_RS + 0] = col ? 1.0 : 0.0;
+      L.red[lane * DD_RS + 1] = mdist;
     }
     __syncthreads();
     if (active && i == 0) {
       double res = 0.0;
       for (int r = 0; r < 6; ++r) {
         double s = 0.0;
-        for (int k = 0; k < n; ++k) s += fabs(E[(ls * n + k) * DD_ES + r]);
+        for (int k = 0; k < n; ++k) s += fabs(L.E[(ls * n + k) * DD_ES + r]);
         res = fmax(res, s);
       }
       const bool stop = (res < a.res_tol) || (iter > a.max_iter);
       if (!stop && a.record_err && a.err) a.err[(size_t)sc * (a.max_iter + 1) + iter - 1] = res;
-      done[ls] = stop ? 1 : 0;
+      L.done[ls] = stop ? 1 : 0;
     }
     __syncthreads();
     if (active) {
-      if (!done[ls]) {
+      if (!L.done[ls]) {
         // dual ascent: lambda += H^-1 (A x)   (control/rqp_dd.py:678-693); rows 6i..6i+5
         // The six rows are read agent block by agent block (18 16-byte loads in flight per block, rows
         // and blocks 48-byte aligned), each row's sum kept in the original order c = 0 .. 6n-1.
@@ -1437,7 +1464,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
           for (int r = 0; r < 6; ++r)
 #pragma unroll
             for (int j = 0; j < 3; ++j) h[r][j] = *(const dat_d2*)(Hi + (size_t)r * N6 + 6 * k + 2 * j);
-          const double* e = E + (ls * n + k) * DD_ES;
+          const double* e = L.E + (ls * n + k) * DD_ES;
           double ev[6];
 #pragma unroll
           for (int j = 0; j < 6; ++j) ev[j] = e[j];
@@ -1464,12 +1491,12 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
         a.qstatus[(size_t)sc * n + i] = qstat;
         if (i == 0) {
           a.iters[sc] = iter;
-          a.ipmx[sc] = wmx[ls];
+          a.ipmx[sc] = L.wmx[ls];
           int coll = 0;
           double md = prm[DAT_P_VISR];
           for (int k = 0; k < n; ++k) {
-            coll |= red[(ls * n + k) * DD_RS] != 0.0;
-            md = fmin(md, red[(ls * n + k) * DD_RS + 1]);
+            coll |= L.red[(ls * n + k) * DD_RS] != 0.0;
+            md = fmin(md, L.red[(ls * n + k) * DD_RS + 1]);
           }
           a.col[sc] = (unsigned char)coll;
           a.mind[sc] = md;
@@ -1486,10 +1513,10 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
           if (i == 0) {
             build_shared(S, prm, n, a.state + (size_t)sc * a.S, a.acc + ((size_t)kstep * a.B + sc) * 6,
                          prm[DAT_P_KFD], prm[DAT_P_KMD], 3, false);
-            wmx[ls] = 0;
+            L.wmx[ls] = 0;
           }
         } else if (i == 0) {
-          sid[ls] = -1;
+          L.sid[ls] = -1;
         }
       }
     }
@@ -2094,6 +2121,37 @@ struct dat_handle {
   std::vector<hipEvent_t> events;
 };
 
+// ---- the handle's per-scenario arrays --------------------------------------------------------------------------
+// Every device array of the handle that holds a fixed number of elements per scenario, scenario-major, has its
+// extent stated once: the checkpointed fp64 arrays in dat_ckpt.hpp (DAT_CK_FIELDS_*: words per scenario), the
+// others here, per mode, as X(array, elements per scenario); the element type is the member's, and KArgs names
+// its member like the handle.  dat_create's allocations, kargs' pointers and sub_kargs' views are written from
+// these lists and from nothing else: a new array is one line here plus its two members.  Beyond the lists only
+// the kernel that indexes an array knows its stride.  (counter and iters: the ints of a checkpoint record,
+// DAT_CK_INT_FIELDS, which states no extent.  erows: SoA over the scenarios of a sub-batch, KArgs::erows.)
+#define DAT_ARRAYS_ALL(X, n) X(counter, 1) X(iters, 1) X(acc, 6) X(qstatus, n) X(mind, 1) X(col, 1)
+#define DAT_ARRAYS_CADMM(X, n)                                                              \
+  X(need, 1) X(ipmx, 1) X(slist, 1) X(rlist, 1) X(done, 1) X(adv, 1) X(rres, RRES_INTS)     \
+  X(erows, 4 * DAT_NENV * (n)) X(emask, n) X(wrec, (n) * WREC_SIZE) X(best, (n) * BEST_REC)
+#define DAT_ARRAYS_DD(X, n)                                     \
+  X(need, 1) X(ipmx, 1) X(slist, 1) X(dHinv, 36 * (n) * (n))    \
+  X(wrec, DAT_DD_WARM ? (n) * WREC_SIZE : 0) X(best, (n) * BEST_REC)
+#define DAT_ARRAYS_CENT(X, n) X(best, NMAX_CENT * BEST_REC)
+// Both lists of `mode` (a run-time value) through the caller's DAT_ARR(array, elements per scenario), a statement
+#define DAT_ARR_CK(arr, words, off) DAT_ARR(arr, words)
+#define DAT_ARRAYS_OF(mode, n)                \
+  do {                                        \
+    DAT_CK_FIELDS_OF(mode, DAT_ARR_CK, n);    \
+    DAT_ARRAYS_ALL(DAT_ARR, n)                \
+    if ((mode) == DAT_MODE_CADMM) {           \
+      DAT_ARRAYS_CADMM(DAT_ARR, n)            \
+    } else if ((mode) == DAT_MODE_DD) {       \
+      DAT_ARRAYS_DD(DAT_ARR, n)               \
+    } else {                                  \
+      DAT_ARRAYS_CENT(DAT_ARR, n)             \
+    }                                         \
+  } while (0)
+
 // C-ADMM scenario slots per k_cadmm wavefront: floor(64/n), fewer when the batch would not give
 // every CU a wavefront.  A small batch is then spread one wavefront per CU (a wavefront's ADMM pass
 // waits for the slowest of fewer lanes).  Not further: wavefronts sharing a CU pair's instruction
@@ -2123,6 +2181,27 @@ void dfree(dat_handle* h, void* p) {
   for (auto& q : h->allocs)
     if (q == p) q = nullptr;
   (void)hipFree(p);
+}
+
+// err, the residual record (record_err handles only; dat_set_max_iter regrows it): elements per scenario
+size_t err_extent(int max_iter) { return (size_t)max_iter + 1; }
+// elements per scenario of the array behind the handle's member *member, as the lists state it
+size_t extent_of(const dat_handle* h, const void* member) {
+  size_t e = 0;
+#define DAT_ARR(arr, per) \
+  if ((const void*)&h->arr == member) e = (size_t)(per);
+  DAT_ARRAYS_OF(h->cfg.mode, h->cfg.n);
+#undef DAT_ARR
+  return e;
+}
+// the scenarios [off, off + count) of sub-batch s of S: contiguous ranges that tile the batch
+struct SubRange {
+  int off, count;
+};
+SubRange sub_range(int batch, int s, int S) {
+  const long long B = batch;
+  const int off = (int)(B * s / S);
+  return {off, (int)(B * (s + 1) / S) - off};
 }
 
 // a timed event of the handle's, made on first use
@@ -2183,11 +2262,12 @@ KArgs kargs(const dat_handle* h) {
   a.P = h->P;
   a.S = h->S;
   a.ppp = h->ppp;
+  // the per-scenario arrays, from the lists; those the mode does not have stay null
+#define DAT_ARR(arr, per) a.arr = h->arr;
+  DAT_ARRAYS_OF(c.mode, c.n);
+#undef DAT_ARR
+  a.done = a.adv = nullptr;  // the advance overlap's stamps are handed over where it runs (adv_args)
   a.params = h->params;
-  a.state = h->state;
-  a.counter = h->counter;
-  a.acc = h->acc;
-  a.fdes = h->fdes;
   a.trees = h->trees;
   a.tree_off = h->tree_off;
   a.scen_forest = h->scen_forest;
@@ -2202,31 +2282,10 @@ KArgs kargs(const dat_handle* h) {
   a.record_err = c.record_err;
   a.qp_tol = h->qp_tol;
   a.ksteps = 1;
-  a.cf = h->cf;
-  a.cfbar = h->cfbar;
-  a.clam = h->clam;
-  a.dlamF = h->dlamF;
-  a.dlamM = h->dlamM;
-  a.dprev = h->dprev;
-  a.dHinv = h->dHinv;
-  a.pf = h->pf;
-  a.best = h->best;
-  a.iters = h->iters;
-  a.qstatus = h->qstatus;
-  a.mind = h->mind;
-  a.col = h->col;
   a.err = h->err;
   a.counters = h->counters;
-  a.need = h->need;
-  a.ipmx = h->ipmx;
-  a.erows = h->erows;
-  a.emask = h->emask;
-  a.slist = h->slist;
   a.scount = h->scount;
-  a.rlist = h->rlist;
-  a.rres = h->rres;
   a.ll_kind = h->ll_kind;
-  a.wrec = h->wrec;
   a.tail_prev = h->nforest > 0 ? TAIL_PREV : INT_MAX;
   a.tail_pass = h->nforest > 0 ? TAIL_PASS : INT_MAX;
   a.route = tail_wanted(h) && h->tail.st;  // (no stream: the wedged scenarios go through k_cadmm's hand-over, same results)
@@ -2238,16 +2297,8 @@ KArgs kargs(const dat_handle* h) {
   return a;
 }
 
-size_t dd_lds(int n, bool env) {
-  int G = 64 / n, NT = G * n;
-  return sizeof(double) * (al2((size_t)NT * 9) + 2 * al2((size_t)G * 3 * n) + al2((size_t)NT * DD_ES) +
-                           (size_t)G * RT_STRIDE * n + 64 * DD_RS) +
-         sizeof(QPShared) * (size_t)G + sizeof(double) * dd_area_doubles(env) + sizeof(int) * 192;
-}
-size_t dd_setup_lds(int n) {
-  int N = 6 * n;
-  return sizeof(double) * (81 * (size_t)n + 9 * (size_t)n + dd_setup_hs(n) + N);
-}
+size_t dd_lds(int n, bool env) { return dd_carve(nullptr, n, env).bytes(); }
+size_t dd_setup_lds(int n) { return dd_setup_carve(nullptr, n).bytes(); }
 
 // the C-ADMM drain of one control step: k_cadmm (env classes 3, 2, 1, 0) with a forest, k_cadmm0 without.
 // k_cadmm_tail: one scenario slot per block (G = 1).  Its scenarios are few -- stalled ADMM loops next to trees,
@@ -2305,40 +2356,23 @@ int launch_dd(const dat_handle* h, const KArgs& a, hipStream_t st, hipEvent_t ek
   return 0;
 }
 
-// kernel arguments of the sub-batch of scenarios [off, off + Bs) (dat_set_sub_batches; the whole batch: those of
-// kargs): every per-scenario array offset, the env-row image a disjoint block of the SoA buffer (stride Bs n), the
-// class table its own; counters shared (atomics)
+// kernel arguments of sub-batch s, the scenarios r (dat_set_sub_batches; the whole batch: those of kargs): every
+// per-scenario array offset by the lists' extents (the env-row image then a disjoint block of the SoA buffer,
+// stride r.count n), the class table its own; counters shared (atomics)
 template <class T>
 T* offp(T* p, size_t k) { return p ? p + k : p; }
-KArgs sub_kargs(const dat_handle* h, int off, int Bs, int s) {
+KArgs sub_kargs(const dat_handle* h, SubRange r, int s) {
   KArgs a = kargs(h);
-  const size_t n = h->cfg.n, N3 = 3 * n, o = (size_t)off;
-  a.B = Bs;
-  a.G = cadmm_slots(h, Bs, (int)n);
+  const size_t o = (size_t)r.off;
+  a.B = r.count;
+  a.G = cadmm_slots(h, r.count, a.n);
+#define DAT_ARR(arr, per) a.arr = offp(a.arr, o * (size_t)(per));
+  DAT_ARRAYS_OF(h->cfg.mode, a.n);
+#undef DAT_ARR
   if (a.ppp) a.params += o * a.P;
-  a.state += o * a.S;
-  a.counter += o;
-  a.acc += o * 6;
-  a.fdes += o * N3;
   a.scen_forest = offp(a.scen_forest, o);
-  a.cf += o * n * N3;
-  a.cfbar += o * N3;
-  a.clam += o * n * N3;
-  a.best += o * n * best_size(1);
-  a.iters += o;
-  a.qstatus += o * n;
-  a.mind += o;
-  a.col += o;
-  a.err = offp(a.err, o * (a.max_iter + 1));
-  a.need += o;
-  a.ipmx += o;
-  a.slist += o;
-  a.rlist += o;
-  a.rres += o * RRES_INTS;
-  a.wrec += o * n * WREC_SIZE;
+  a.err = offp(a.err, o * err_extent(a.max_iter));
   a.scount = h->scount + SCOUNT_INTS * s;
-  a.erows += (size_t)4 * DAT_NENV * n * o;
-  a.emask += o * n;
   return a;
 }
 
@@ -2395,14 +2429,22 @@ struct Sub {
   hipEvent_t ek, e1;
 };
 Sub sub_batch(const dat_handle* h, int s = 0, int S = 1) {
-  const long long B = h->cfg.batch;
+  const SubRange r = sub_range(h->cfg.batch, s, S);
   Sub u;
   u.st = h->sub[s].st;
-  u.off = (int)(B * s / S);
-  u.a = sub_kargs(h, u.off, (int)(B * (s + 1) / S) - u.off, s);
+  u.off = r.off;
+  u.a = sub_kargs(h, r, s);
   u.ek = h->ek;
   u.e1 = h->e1;
   return u;
+}
+// ... with the closed loop's advance overlap switched on (one sub-batch: the whole batch)
+void adv_args(const dat_handle* h, KArgs& a) {
+  a.done = h->done;
+  a.adv = h->adv;
+  a.qempty = h->qempty_dev;
+  a.advmask = h->advmask;
+  a.advcnt = h->advcnt;
 }
 
 // What every entry point that runs control steps starts with.  The tail stream is made here, on first use.
@@ -2586,11 +2628,7 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
     h->sub_ev.push_back(e);
   }
   Sub base = sub_batch(h);
-  base.a.done = h->done;
-  base.a.adv = h->adv;
-  base.a.qempty = h->qempty_dev;
-  base.a.advmask = h->advmask;
-  base.a.advcnt = h->advcnt;
+  adv_args(h, base.a);
   // the main drain of step k: on the handle's stream over every scenario (k = 0, the first of the call), else on
   // the stream of the early pass it follows
   const auto main_drain = [&](int k, int serial) {
@@ -2871,33 +2909,18 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.device) == hipSuccess && ncu > 0)
     h->persistent_blocks = 4 * ncu;  // k_cadmm: one wavefront per SIMD (register-bound), 4 SIMDs per CU
-  const size_t B = c.batch, n = c.n, N3 = 3 * n;
+  const size_t B = c.batch;
   int rc = 0;
-  rc |= dalloc(h, &h->state, B * h->S);
-  rc |= dalloc(h, &h->counter, B);
-  rc |= dalloc(h, &h->acc, B * 6);
-  rc |= dalloc(h, &h->fdes, B * N3);
-  rc |= dalloc(h, &h->iters, B);
-  rc |= dalloc(h, &h->qstatus, B * n);
-  rc |= dalloc(h, &h->mind, B);
-  rc |= dalloc(h, &h->col, B);
+  // the per-scenario arrays of the mode, from the lists
+#define DAT_ARR(arr, per) rc |= dalloc(h, &h->arr, B * (size_t)(per));
+  DAT_ARRAYS_OF(c.mode, c.n);
+#undef DAT_ARR
+  if (c.record_err) rc |= dalloc(h, &h->err, B * err_extent(c.max_iter));
+  // the others: the counters, the queues' class tables (C-ADMM: one per sub-batch), the advance overlap's words
   rc |= dalloc(h, &h->counters, DAT_NCOUNTERS);
-  if (c.record_err) rc |= dalloc(h, &h->err, B * (c.max_iter + 1));
+  if (c.mode != DAT_MODE_CENTRALIZED)
+    rc |= dalloc(h, &h->scount, SCOUNT_INTS * (c.mode == DAT_MODE_CADMM ? DAT_MAX_SUB : 1));
   if (c.mode == DAT_MODE_CADMM) {
-    rc |= dalloc(h, &h->need, B);
-    rc |= dalloc(h, &h->ipmx, B);
-    rc |= dalloc(h, &h->erows, (size_t)B * n * DAT_NENV * 4);
-    rc |= dalloc(h, &h->emask, (size_t)B * n);
-    rc |= dalloc(h, &h->slist, B);
-    rc |= dalloc(h, &h->scount, SCOUNT_INTS * DAT_MAX_SUB);  // one class table per sub-batch
-    rc |= dalloc(h, &h->cf, B * n * N3);
-    rc |= dalloc(h, &h->cfbar, B * N3);
-    rc |= dalloc(h, &h->clam, B * n * N3);
-    rc |= dalloc(h, &h->rres, B * RRES_INTS);
-    rc |= dalloc(h, &h->rlist, B);
-    rc |= dalloc(h, &h->wrec, B * n * WREC_SIZE);
-    rc |= dalloc(h, &h->done, B);
-    rc |= dalloc(h, &h->adv, B);
     rc |= dalloc(h, &h->advcnt, 2);
     // (without the host word the closed loop keeps the serial schedule)
     if (hipHostMalloc((void**)&h->qempty, sizeof(int), hipHostMallocMapped) == hipSuccess) {
@@ -2907,30 +2930,8 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
       h->qempty = nullptr;
       (void)hipGetLastError();
     }
-  } else if (c.mode == DAT_MODE_DD) {
-    rc |= dalloc(h, &h->need, B);
-    rc |= dalloc(h, &h->ipmx, B);
-    rc |= dalloc(h, &h->slist, B);
-    rc |= dalloc(h, &h->scount, SCOUNT_INTS);
-    rc |= dalloc(h, &h->dlamF, B * N3);
-    rc |= dalloc(h, &h->dlamM, B * N3);
-    rc |= dalloc(h, &h->dprev, B * n * 9);
-#if DAT_DD_WARM
-    rc |= dalloc(h, &h->wrec, B * n * WREC_SIZE);
-#endif
-    rc |= dalloc(h, &h->dHinv, B * 36 * n * n);
-  } else {
-    rc |= dalloc(h, &h->pf, B * N3);
   }
-  // lane-private IPM best-iterate records
-  // best-iterate records: one per agent QP lane (centralized: one per lane of the scenario's 16-lane slot)
-  rc |= dalloc(h, &h->best, c.mode == DAT_MODE_CENTRALIZED ? B * 16 * (size_t)best_size(1) : B * n * (size_t)best_size(1));
-  if (rc) {
-    std::string m = g_err;
-    dat_destroy(h);
-    return fail(m);
-  }
-  if (dat_reset_counters(h)) {
+  if (rc || dat_reset_counters(h)) {
     std::string m = g_err;
     dat_destroy(h);
     return fail(m);
@@ -3063,7 +3064,7 @@ int dat_set_max_iter(dat_handle* h, int max_iter) {
     HIPCHK(hipStreamSynchronize(h->stream));
     dfree(h, h->err);
     h->err = nullptr;
-    if (dalloc(h, &h->err, (size_t)h->cfg.batch * (max_iter + 1))) return -1;
+    if (dalloc(h, &h->err, (size_t)h->cfg.batch * err_extent(max_iter))) return -1;
   }
   h->cfg.max_iter = max_iter;
   return 0;
@@ -3274,14 +3275,7 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
   const size_t ndrain = S > 1 && hl_steps > 0 ? (size_t)S * hl_steps : 0;
   Sub u[DAT_MAX_SUB];
   for (int s = 0; s < S; ++s) u[s] = sub_batch(h, s, S);
-  if (overlap) {
-    KArgs& a = u[0].a;
-    a.done = h->done;
-    a.adv = h->adv;
-    a.qempty = h->qempty_dev;
-    a.advmask = h->advmask;
-    a.advcnt = h->advcnt;
-  }
+  if (overlap) adv_args(h, u[0].a);
   h->marks.assign(1, now_ms());
   if (S > 1) {  // a drain event pair per step and sub-batch; the sub-batch streams start after the handle's
     while (h->sub_ev.size() < 2 * ndrain) {
@@ -3470,9 +3464,9 @@ int dat_debug_get_env_class(dat_handle* h, double* lhs, double* rhs, int* nrow, 
   if (h->env_sub < 1) return fail("dat_debug_get_env_class: no control step has run");
   HIPCHK(hipSetDevice(h->cfg.device));
   for (hipStream_t st : h->streams) HIPCHK(hipStreamSynchronize(st));  // (the handle's own among them)
-  const size_t B = h->cfg.batch, n = h->cfg.n, per = (size_t)4 * DAT_NENV * n;
+  const size_t B = h->cfg.batch, n = h->cfg.n, per = extent_of(h, &h->erows);
   std::vector<double> img(B * per);
-  std::vector<unsigned> mask(B * n);
+  std::vector<unsigned> mask(B * extent_of(h, &h->emask));
   std::vector<int> need(B);
   HIPCHK(hipMemcpy(img.data(), h->erows, sizeof(double) * img.size(), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(mask.data(), h->emask, sizeof(unsigned) * mask.size(), hipMemcpyDeviceToHost));
@@ -3480,8 +3474,9 @@ int dat_debug_get_env_class(dat_handle* h, double* lhs, double* rhs, int* nrow, 
   std::fill(lhs, lhs + B * n * DAT_NENV * 3, 0.0);
   std::fill(rhs, rhs + B * n * DAT_NENV, 0.0);
   const int S = h->env_sub;
-  for (int s = 0; s < S; ++s) {  // the sub-batch's block of the image (sub_batch, sub_kargs): stride Bs n
-    const size_t off = (size_t)((long long)B * s / S), NA = ((size_t)((long long)B * (s + 1) / S) - off) * n;
+  for (int s = 0; s < S; ++s) {  // the sub-batch's block of the image (sub_kargs): stride count n
+    const SubRange r = sub_range(h->cfg.batch, s, S);
+    const size_t off = (size_t)r.off, NA = (size_t)r.count * n;
     const double* blk = img.data() + per * off;
     for (size_t g = 0; g < NA; ++g) {
       const size_t t = off * n + g;  // scenario-major index of the agent in the whole batch

@@ -70,6 +70,10 @@ __host__ __device__ constexpr int sc_at(ScountRow row, int cls) { return row * N
 // stopped in, the IPM-iteration maximum so far, and the mask of its agent lanes whose solve of that pass
 // was not clean (the others' results of the pass stand; -1: all, a hand-over between passes by the tail rule)
 constexpr int RRES_KSTEP = 0, RRES_PASS = 1, RRES_WMX = 2, RRES_LANES = 3, RRES_INTS = 4;
+// A lane's record in KArgs::best: the best iterate alone, all a fast solve touches (best_rec, dat_qp.hpp; the
+// robust solver's scratch behind it lives in the tail's LDS and in k_agent_qp's own buffer).  Lanes per scenario:
+// n, centralized NMAX_CENT.
+constexpr int BEST_REC = best_rec(1);
 constexpr double INBAND_CLARABEL = IPM_CLARABEL_TOL;
 __device__ inline int inband_loose(const IPMOut& o) { return o.inband && o.merit > INBAND_CLARABEL; }
 
@@ -93,7 +97,7 @@ struct KArgs {
   double *cf, *cfbar, *clam;                 // C-ADMM warm state
   double *dlamF, *dlamM, *dprev, *dHinv;      // DD state
   double* pf;                                 // centralized previous solution
-  double* best;                               // lane-private best-iterate records of the IPM
+  double* best;                               // lane-private best-iterate records of the IPM (BEST_REC doubles each)
   int* iters;
   int* qstatus;
   double* mind;

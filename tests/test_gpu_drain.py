@@ -194,23 +194,49 @@ def test_gpu_closed_loop_sub_batches_bitwise(subs):
     """dat_set_sub_batches: the C4 closed loop (desired acceleration, env classes, class sort, C-ADMM drain,
     rollout) on 2 or 3 sub-batches, each on its own stream with no synchronisation between them, must
     leave every scenario in exactly the state of the single-stream loop after 3 HL steps (a scenario's
-    arithmetic does not depend on its grouping), with the same work counters."""
+    arithmetic does not depend on its grouping), with the same work counters -- and with the same checkpoint of
+    all scenarios, byte for byte: f_des, f, f_mean, lambda_f, iters, ipmx and the counter, every warm array a
+    sub-batch's kernels reach through an offset view of the handle's."""
+    n, B, K = 6, 131, 3
+    one, many = (_sub_batch_run(n, B, K, sb) for sb in (1, subs))
+    _assert_same_run(one, many)
+
+
+def _sub_batch_run(n, B, K, subs, per_scenario_params=False):
+    """K closed-loop HL steps of B near-tree scenarios in four forests on `subs` sub-batches: the final state, the
+    checkpoint blob of all scenarios and the work counters."""
     from distributed_aerial_transportation_amd import BatchedController, Forest, scenarios
     from tests.test_gpu_c4 import near_tree_states
 
-    n, B, K = 6, 131, 3
     forests = [Forest.seeded(s) for s in range(4)]
     sf = np.arange(B) % 4
     x0 = near_tree_states(n, forests, sf, np.random.default_rng(77))
-    out = []
-    for sb in (1, subs):
-        eng = BatchedController("cadmm", n, B, scenarios.params_block(n))
-        eng.set_forests(forests, sf)
-        eng.set_state(x0, np.zeros(B, dtype=np.int32))
-        eng.set_sub_batches(sb)
-        eng.closed_loop(K)
-        st, _ = eng.get_state()
-        out.append((st, eng.work()))
-    np.testing.assert_array_equal(out[0][0], out[1][0])
+    params = scenarios.params_block(n)
+    if per_scenario_params:
+        params = np.tile(params, (B, 1))
+    eng = BatchedController("cadmm", n, B, params, per_scenario_params=per_scenario_params)
+    eng.set_forests(forests, sf)
+    eng.set_state(x0, np.zeros(B, dtype=np.int32))
+    eng.set_sub_batches(subs)
+    eng.closed_loop(K)
+    st, _ = eng.get_state()
+    out = st, eng.checkpoint().tobytes(), eng.work()
+    eng.close()
+    return out
+
+
+def _assert_same_run(a, b):
+    np.testing.assert_array_equal(a[0], b[0])
+    assert a[1] == b[1], "checkpoint blobs differ"
     for key in ("qp_solves", "ipm_iters", "ipm_row_iters", "hl_steps"):
-        assert out[0][1][key] == out[1][1][key], key
+        assert a[2][key] == b[2][key], key
+
+
+def test_gpu_sub_batch_views_smallest_uneven_ranges():
+    """The smallest shape at which a sub-batch's view of the handle's arrays can go wrong: n = 3, B = 7 on four
+    sub-batches, whose ranges hold 1, 2, 2 and 2 scenarios (uneven, one of a single scenario), with per-scenario
+    parameters (their view is offset by the parameter block, the others by the arrays' own extents) and a forest,
+    over 2 HL steps.  Against one sub-batch: the state, the whole checkpoint blob and the work counters equal."""
+    n, B, K = 3, 7, 2
+    one, four = (_sub_batch_run(n, B, K, sb, per_scenario_params=True) for sb in (1, 4))
+    _assert_same_run(one, four)
