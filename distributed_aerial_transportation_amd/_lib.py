@@ -27,7 +27,8 @@ OBJ_DIR = os.path.join(PKG, "build")
 # 3.55 ms per step.
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on"]
 DEPS = [SRC, SRC_CENT, SRC_COMM, os.path.join(PKG, "csrc", "dat_core.hpp"), os.path.join(PKG, "csrc", "dat_qp.hpp"),
-        os.path.join(PKG, "csrc", "dat_cadmm_step.hpp"), os.path.join(PKG, "csrc", "dat_kargs.hpp"),
+        os.path.join(PKG, "csrc", "dat_cadmm_step.hpp"), os.path.join(PKG, "csrc", "dat_dd_step.hpp"),
+        os.path.join(PKG, "csrc", "dat_kargs.hpp"),
         os.path.join(PKG, "csrc", "dat_ckpt.hpp"),
         os.path.join(PKG, "csrc", "dat_layout.h"), os.path.join(REPO, "include", "dat.h")]
 

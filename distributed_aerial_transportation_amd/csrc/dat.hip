@@ -30,6 +30,7 @@
 #include "../../include/dat.h"
 #include "dat_ckpt.hpp"
 #include "dat_kargs.hpp"
+#include "dat_dd_step.hpp"
 
 using namespace dat;
 
@@ -95,18 +96,8 @@ int fail(const std::string& m) {
 // which with the 256 B of static LDS left room for three workgroups per CU (one SIMD idle); four fit after
 // the trim (C4 A/B 3.83 / 3.80 -> 3.72 / 3.77 ms per step), and the budget then went to classes 1 and 2's
 // aux groups at three per CU instead (LDS_WAVE_BUDGET).
-// DD warm start: from DD pass DD_WARM_PASS of a step on, the agent QPs start from the previous pass's iterate (a
-// long DD chain -- C3's slowest scenario runs the reference's cap of 100 passes at every step, the step's
-// critical path; ordinary steps take ~4 passes and never reach it).  Its agent QP differs from the previous pass's
-// only in the prices.  From pass 1 on it cut C3 further but left the n = 3 golden DD error sequence (25 fixed
-// passes) 3e-4 off (bound 1e-4): a warm start lands elsewhere in a weakly convex QP's near-flat minimiser set than
-// the reference's cold solve.  Same-call A/B (C3, ms per step): 21.7 -> 13.4 with DD_WS_MU 1e-3 (1e-2: 14.3);
-// every DD parity test green (golden sequences, the DD hard stretch, the 100 s loop to the same horizon).
-// (DAT_DD_WARM=0: the round-5 cold DD, A/B builds.)
-#ifndef DAT_DD_WARM
-#define DAT_DD_WARM 1
-#endif
-constexpr int DD_WARM_PASS = 30;
+// (The DD warm start -- k_dd's agent QPs start from the previous pass's iterate from pass DD_WARM_PASS on -- is a
+// rule of the DD step: dat_dd_step.hpp states it and what it measured; k_dd has no cold build any more.)
 constexpr int RDS = 7;  // consensus exchange slots per lane: mean (3) or F / M totals (6), total residual at [6]
 // LDS budget of one k_cadmm workgroup: 53 KB = three per CU.  Four per CU (40 KB) bought ~2 % (§5 of
 // DESIGN.md, round 4); the 13 KB more per workgroup hold classes 1 and 2's IPM aux groups in LDS
@@ -914,55 +905,7 @@ __global__ __launch_bounds__(64) void k_cadmm0_tail(KArgs a) { cadmm_drain<0, tr
 // ------------------------------------------------------------------------------------------------
 // DD: quasi-Newton matrix inverse per scenario (one 64-lane block per scenario)
 // ------------------------------------------------------------------------------------------------
-// Q_i: strong_convexity_matrix (control/rqp_dd.py:513-555), 9x9 in (f_i, F_i, M_i)
-__device__ void dd_strong_convexity(const double* prm, int n, const double* st, int i, double* Q) {
-  const double kf = prm[DAT_P_KFD], km = prm[DAT_P_KMD], kfeq = prm[DAT_P_KFEQ];
-  const double leader = (i == 0) ? 1.0 : 0.0;
-  const double mT = prm[DAT_P_MT];
-  const double* Rl = st + DAT_S_RL(n);
-  double Rt[9], Xh[9], RX[9], Bv[9];
-  make_Rt(prm + DAT_P_RCOM(n) + 3 * i, Rl, Rt);
-  skew3(prm + DAT_P_XCOM, Xh);
-  mm3(Rl, Xh, RX);
-  mm3(RX, prm + DAT_P_JTI, Bv);  // Rl hat(x_com) JT^-1
-  for (int k = 0; k < 81; ++k) Q[k] = 0.0;
-  for (int k = 0; k < 9; ++k) Q[10 * k] = 1e-6;
-  auto acc = [&](const double* T /*3x9*/, double wgt) {
-    for (int r = 0; r < 9; ++r)
-      for (int c = 0; c < 9; ++c) Q[9 * r + c] += 2.0 * wgt * (T[r] * T[c] + T[9 + r] * T[9 + c] + T[18 + r] * T[18 + c]);
-  };
-  double T[27];
-  for (int k = 0; k < 27; ++k) T[k] = 0.0;
-  for (int r = 0; r < 3; ++r) T[9 * r + r] = 1.0;          // [I 0 0]
-  acc(T, kfeq);
-  for (int r = 0; r < 3; ++r) T[9 * r + 3 + r] = 1.0;      // [I I 0]
-  acc(T, kf);
-  for (int k = 0; k < 27; ++k) T[k] = 0.0;                 // [Rt 0 I]
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) T[9 * r + c] = Rt[3 * r + c];
-    T[9 * r + 6 + r] = 1.0;
-  }
-  acc(T, km);
-  if (leader != 0.0) {
-    const double* JTi = prm + DAT_P_JTI;
-    double JR[9], BR[9];
-    mm3(JTi, Rt, JR);
-    mm3(Bv, Rt, BR);
-    for (int k = 0; k < 27; ++k) T[k] = 0.0;               // [JT^-1 Rt, 0, JT^-1]
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) { T[9 * r + c] = JR[3 * r + c]; T[9 * r + 6 + c] = JTi[3 * r + c]; }
-    acc(T, leader);
-    for (int k = 0; k < 27; ++k) T[k] = 0.0;               // [I/mT + Bv Rt, I/mT, Bv]
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) {
-        T[9 * r + c] = BR[3 * r + c] + (r == c ? 1.0 / mT : 0.0);
-        T[9 * r + 3 + c] = (r == c ? 1.0 / mT : 0.0);
-        T[9 * r + 6 + c] = Bv[3 * r + c];
-      }
-    acc(T, leader);
-  }
-}
-
+// Q_i (strong_convexity_matrix), the eliminations' per-element steps and the H element: dat_dd_step.hpp
 // k_dd_setup keeps the columns of [H | I] in registers for n <= DD_REG_NMAX (dd_setup_h_regs), in LDS
 // beyond
 constexpr int DD_REG_NMAX = 8;
@@ -998,6 +941,10 @@ __host__ __device__ inline DdSetupLds dd_setup_carve(double* smem, int n) {
 // pivoting (H is SPD), per element hk = h_kc / piv, h_rc -= f_r hk.  The column is kept rotated so
 // that step k's pivot row is element 0 (no runtime register index): the owner of column k publishes it
 // in LDS (double buffered), every lane updates its columns and rotates them by one.
+// The elimination's element steps are the header's (dd_hinv_scale, dd_hinv_eliminate).  The assembly restates
+// dd_arow / dd_h_element by the row's three cases: here the row r is a compile-time index and the column's agent
+// and component are the lane's, so the header's form (a 9-vector per row, zeros skipped by value) would run the
+// sums over runtime zeros and index registers at run time.
 template <int NB>
 __device__ void dd_setup_h_regs(const KArgs& a, int sc, const double* Qi, const double* Rts, double* fac) {
   constexpr int N = 6 * NB;
@@ -1061,17 +1008,17 @@ __device__ void dd_setup_h_regs(const KArgs& a, int sc, const double* Qi, const 
     __syncthreads();
     const double piv = f[0];
     {
-      const double hk = h[0] / piv;
+      const double hk = dd_hinv_scale(h[0], piv);
 #pragma unroll
-      for (int i = 1; i < N; ++i) h[i] -= f[i] * hk;
+      for (int i = 1; i < N; ++i) dd_hinv_eliminate(h[i], f[i], hk);
 #pragma unroll
       for (int i = 0; i < N - 1; ++i) h[i] = h[i + 1];
       h[N - 1] = hk;
     }
     if (TWO) {
-      const double hk = g[0] / piv;
+      const double hk = dd_hinv_scale(g[0], piv);
 #pragma unroll
-      for (int i = 1; i < N; ++i) g[i] -= f[i] * hk;
+      for (int i = 1; i < N; ++i) dd_hinv_eliminate(g[i], f[i], hk);
 #pragma unroll
       for (int i = 0; i < N - 1; ++i) g[i] = g[i + 1];
       g[N - 1] = hk;
@@ -1110,24 +1057,16 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
   if (lane < n) {
     double Q[81];
     dd_strong_convexity(prm, n, st, lane, Q);
-    for (int r = 0; r < 9; ++r)
-      for (int c = 0; c < 18; ++c) Aug[162 * lane + 18 * r + c] = c < 9 ? Q[9 * r + c] : (c - 9 == r ? 1.0 : 0.0);
+    dd_qinv_augment(Q, Aug + 162 * lane);
     make_Rt(prm + DAT_P_RCOM(n) + 3 * lane, st + DAT_S_RL(n), L.Rts + 9 * lane);
   }
   __syncthreads();
   for (int k = 0; k < 9; ++k) {
-    if (lane < n) {
-      const double* A = Aug + 162 * lane;
-      int p = k;
-      for (int r = k + 1; r < 9; ++r)
-        if (fabs(A[18 * r + k]) > fabs(A[18 * p + k])) p = r;
-      pivr[lane] = p;
-    }
+    if (lane < n) pivr[lane] = dd_qinv_pivot_row(Aug + 162 * lane, k);
     __syncthreads();
     for (int e = lane; e < 18 * n; e += 64) {  // row exchange k <-> p, column by column
-      const int j = e / 18, c = e - 18 * j, p = pivr[j];
-      double* A = Aug + 162 * j;
-      if (p != k) { double t = A[18 * k + c]; A[18 * k + c] = A[18 * p + c]; A[18 * p + c] = t; }
+      const int j = e / 18, c = e - 18 * j;
+      dd_qinv_exchange(Aug + 162 * j, k, pivr[j], c);
     }
     __syncthreads();
     for (int e = lane; e < 9 * n; e += 64) {
@@ -1137,58 +1076,23 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
     __syncthreads();
     for (int e = lane; e < 18 * n; e += 64) {
       const int j = e / 18, c = e - 18 * j;
-      double* A = Aug + 162 * j;
-      const double inv = 1.0 / colk[9 * j + k];
-      const double hk = A[18 * k + c] * inv;
-      A[18 * k + c] = hk;
-      for (int r = 0; r < 9; ++r)
-        if (r != k) A[18 * r + c] -= colk[9 * j + r] * hk;
+      dd_qinv_update_col(Aug + 162 * j, colk + 9 * j, k, c);
     }
     __syncthreads();
   }
   for (int e = lane; e < 81 * n; e += 64) {
     const int j = e / 81, rc = e - 81 * j, r = rc / 9, c = rc - 9 * r;
-    const double* A = Aug + 162 * j;
-    L.Qi[e] = 0.5 * (A[18 * r + 9 + c] + A[18 * c + 9 + r]);
+    L.Qi[e] = dd_qinv_sym(Aug + 162 * j, r, c);
   }
   __syncthreads();
   if constexpr (NB > 0) {
     dd_setup_h_regs<NB>(a, sc, L.Qi, L.Rts, L.H + 171 * n + 1);  // pivot columns past the Q_i elimination area
     return;
   }
-  // H = A blkdiag(Q_j^-1) A'  (control/rqp_dd.py:642-655); row r of A restricted to block j:
-  //   j == agent(r): unit vector e_{3 + comp};  j != agent(r): -e_comp (comp < 3) or -Rt_j[comp-3, :] on f_j
-  // every index below is compile-time after unrolling, so v stays in registers (no scratch)
-  auto arow = [&](int r, int j, double* v) {
-    const int ag = r / 6, comp = r % 6;
-    const double* rt = L.Rts + 9 * j + 3 * (comp >= 3 ? comp - 3 : 0);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      double x = 0.0;
-      if (j == ag) x = (k == 3 + comp) ? 1.0 : 0.0;
-      else if (comp < 3) x = (k == comp) ? -1.0 : 0.0;
-      else if (k < 3) x = -rt[k];
-      v[k] = x;
-    }
-  };
+  // H = A blkdiag(Q_j^-1) A'  (control/rqp_dd.py:642-655)
   for (int e = lane; e < N * N; e += 64) {
     int r = e / N, c = e % N;
-    double s = 0.0;
-    for (int j = 0; j < n; ++j) {
-      double vr[9], vc[9];
-      arow(r, j, vr);
-      arow(c, j, vc);
-      const double* Q = L.Qi + 81 * j;
-#pragma unroll
-      for (int p = 0; p < 9; ++p) {
-        if (vr[p] == 0.0) continue;
-        double t = 0.0;
-#pragma unroll
-        for (int q = 0; q < 9; ++q) t += Q[9 * p + q] * vc[q];
-        s += vr[p] * t;
-      }
-    }
-    L.H[2 * N * r + c] = s;
+    L.H[2 * N * r + c] = dd_h_element(L.Qi, L.Rts, n, r, c);
     L.H[2 * N * r + N + c] = (r == c) ? 1.0 : 0.0;
   }
   __syncthreads();
@@ -1199,12 +1103,7 @@ __global__ __launch_bounds__(64) void k_dd_setup(KArgs a) {
     double piv = L.H[2 * N * k + k];
     for (int r = lane; r < N; r += 64) L.fac[r] = L.H[2 * N * r + k];
     __syncthreads();
-    for (int c = lane; c < 2 * N; c += 64) {
-      const double hk = L.H[2 * N * k + c] / piv;
-      L.H[2 * N * k + c] = hk;
-      for (int r = 0; r < N; ++r)
-        if (r != k) L.H[2 * N * r + c] -= L.fac[r] * hk;
-    }
+    for (int c = lane; c < 2 * N; c += 64) dd_hinv_update_col(L.H, 2 * N, N, L.fac, piv, k, c);
     __syncthreads();
   }
   double* out = a.dHinv + (size_t)sc * N * N;
@@ -1247,8 +1146,7 @@ __host__ __device__ inline DdLds dd_carve(double* smem, int n, bool env) {
 }
 // k_dd_key: drain-order key of every scenario -- the previous step's (DD iteration count, slowest agent
 // QP's IPM iterations), longest first, as k_cadmm's key -- sorted by k_bucket into one queue (class 0).
-// DD agent QPs run the conservative IPM start (9-10 iterations on average): bins <= 8, 9-10, 11-13, >= 14.
-__host__ __device__ inline int dd_ipm_bin(int it) { return it <= 8 ? 0 : it <= 10 ? 1 : it <= 13 ? 2 : 3; }
+// (dd_ipm_bin: dat_dd_step.hpp)
 __global__ void k_dd_key(KArgs a) {
   const int sc = blockIdx.x * blockDim.x + threadIdx.x;
   if (sc < a.B) a.need[sc] = NIB - 1 - (NPB * iter_bin(a.iters[sc]) + dd_ipm_bin(a.ipmx[sc]));
@@ -1271,6 +1169,8 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
   const DdLds L = dd_carve(smem, n, ENV);
   QPShared& S = L.shs[lsc];
   double* myX = L.X + lane * 9;
+  const double* Xs = L.X + lsc * n * 9;  // the slot's agent records (dat_dd_step.hpp)
+  const double* Es = L.E + lsc * n * DD_ES;
   double* lF = L.lamF + lsc * N3;
   double* lM = L.lamM + lsc * N3;
   double* rts = L.Rts + lsc * RT_STRIDE * n;
@@ -1285,7 +1185,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
   const double* prm = nullptr;
   const double* Rl = nullptr;
   double* bst = nullptr;
-  double* wrl = nullptr;  // DAT_DD_WARM: the agent QP's warm-start record (HBM)
+  double* wrl = nullptr;  // the agent QP's warm-start record (HBM)
   double prev[9];
   int sc = -1, iter = 0, qstat = ST_OPTIMAL, col = 0;
   int kstep = 0;  // fused control steps (dat_control_steps): the slot scenario's current step
@@ -1319,10 +1219,8 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       for (int c = 0; c < 9; ++c) prev[c] = a.dprev[((size_t)sc * n + i) * 9 + c];
       for (int c = 0; c < 9; ++c) myX[c] = prev[c];  // the controller's current (f, F, M)
       bst = a.best + ((size_t)sc * n + i) * BEST_REC;
-#if DAT_DD_WARM
       wrl = a.wrec + ((size_t)sc * n + i) * WREC_SIZE;
       wrl[0] = 0.0;
-#endif
       iter = 0;
       qstat = ST_OPTIMAL;
       kstep = 0;
@@ -1351,42 +1249,22 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
     const int nr = wave_max(active ? rows_needed(P.emask) : NBASE);
     DAT_PHASE(14);
     if (active) {
-      // prices (control/rqp_dd.py:718-722)
-      double sF[3] = {0, 0, 0}, sM[3] = {0, 0, 0};
-      for (int k = 0; k < n; ++k)
-        for (int c = 0; c < 3; ++c) { sF[c] += lF[3 * k + c]; sM[c] += lM[3 * k + c]; }
-      double c9[9], dm[3], rxd[3], Rr[3];
-      for (int c = 0; c < 3; ++c) dm[c] = sM[c] - lM[3 * i + c];
-      cross3(prm + DAT_P_RCOM(n) + 3 * i, dm, rxd);
-      mv3(Rl, rxd, Rr);
-      for (int c = 0; c < 3; ++c) {
-        c9[c] = -(sF[c] - lF[3 * i + c]) + Rr[c];
-        c9[3 + c] = lF[3 * i + c];
-        c9[6 + c] = lM[3 * i + c];
-      }
+      double c9[9];
+      dd_prices(prm, n, i, lF, lM, Rl, c9);
       set_dd_price(P, prm, n, i, c9);
       double y[1][3], w[6];
       IPMOut o;
       const double* y0 = prm + DAT_P_FEQ(n) + 3 * i;
       DAT_PHASE(10);
-#if DAT_DD_WARM
-      // a DD pass after the first: the agent QP differs from the previous pass's only in its prices, so it starts
-      // from that pass's last iterate (ipm_solve WS, the tail kernel's warm start)
-      const bool wson = iter >= DD_WARM_PASS;
+      // a late DD pass: the agent QP differs from the previous pass's only in its prices, so it starts from that
+      // pass's last iterate (ipm_solve WS, the tail kernel's warm start)
+      const bool wson = dd_warm_pass(iter);
       if constexpr (ENV)
         o = ipm_solve_rows<MODE_DD, 1, IPM_FAST, true>(nr, shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER, a.qp_tol,
                                                        wrl, wson);
       else
         o = ipm_solve<MODE_DD, 1, NBASE, LdsRef<QPShared>, EnvLds, RtLds, RowRegs, 0, NoGrp, IPM_FAST, true>(
             shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowRegs{}, NoGrp{}, wrl, wson);
-#else
-      if constexpr (ENV)
-        o = ipm_solve_rows<MODE_DD, 1>(nr, shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER,
-                                       a.qp_tol);
-      else
-        o = ipm_solve<MODE_DD, 1, NBASE>(shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER,
-                                         a.qp_tol);
-#endif
       DAT_PHASE(9);
       wc.ipm += o.iters;
       wc.inband += o.inband;
@@ -1400,19 +1278,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       wc.rowit += (long long)o.iters * (__builtin_popcount(S.bmask) + __builtin_popcount(P.emask));
       ++wc.qp;
       qstat = o.status;
-      if (o.status == ST_OPTIMAL) {
-        for (int c = 0; c < 3; ++c) prev[c] = y[0][c];
-        for (int c = 0; c < 6; ++c) prev[3 + c] = w[c];
-      } else if (o.status == ST_FAILED) {  // control/rqp_dd.py:484-489
-        // Quirk a15: the controller's f aliases solver 0's f_eq (control/rqp_dd.py:629, written in
-        // place at :725), so agent 0's fallback sums the controller's current forces (every agent's
-        // f before this iteration's writes); the other agents sum their own f_eq.
-        const double* feq = prm + DAT_P_FEQ(n);
-        double s3[3] = {0, 0, 0};
-        for (int k = 0; k < n; ++k)
-          for (int c = 0; c < 3; ++c) s3[c] += (i == 0) ? L.X[(ls * n + k) * 9 + c] : feq[3 * k + c];
-        dd_fallback(prm, n, i, s3, prev);
-      }
+      dd_take_solve(o.status, y[0], w, prm, n, i, Xs, prev);
     }
     DAT_PHASE(13);
     __syncthreads();  // agent 0's fallback above reads X before this pass's writes
@@ -1422,64 +1288,21 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
     __syncthreads();
     if (active) {
       ++iter;
-      // consensus error (control/rqp_dd.py:659-676)
-      double sf[3] = {0, 0, 0}, sm[3] = {0, 0, 0};
-      for (int k = 0; k < n; ++k) {
-        if (k == i) continue;
-        const double* fk = L.X + (ls * n + k) * 9;
-        double m3[3];
-        mv3(rts + RT_STRIDE * k, fk, m3);
-        for (int c = 0; c < 3; ++c) { sf[c] += fk[c]; sm[c] += m3[c]; }
-      }
-      for (int c = 0; c < 3; ++c) {
-        L.E[lane * DD_ES + c] = myX[3 + c] - sf[c];
-        L.E[lane * DD_ES + 3 + c] = myX[6 + c] - sm[c];
-      }
+      dd_consensus_error(Xs, rts, RT_STRIDE, n, i, L.E + lane * DD_ES);
       L.red[lane * DD_RS + 0] = col ? 1.0 : 0.0;
       L.red[lane * DD_RS + 1] = mdist;
     }
     __syncthreads();
     if (active && i == 0) {
-      double res = 0.0;
-      for (int r = 0; r < 6; ++r) {
-        double s = 0.0;
-        for (int k = 0; k < n; ++k) s += fabs(L.E[(ls * n + k) * DD_ES + r]);
-        res = fmax(res, s);
-      }
-      const bool stop = (res < a.res_tol) || (iter > a.max_iter);
+      const double res = dd_pass_residual(Es, DD_ES, n);
+      const bool stop = dd_stop(res, a.res_tol, iter, a.max_iter);
       if (!stop && a.record_err && a.err) a.err[(size_t)sc * (a.max_iter + 1) + iter - 1] = res;
       L.done[ls] = stop ? 1 : 0;
     }
     __syncthreads();
     if (active) {
       if (!L.done[ls]) {
-        // dual ascent: lambda += H^-1 (A x)   (control/rqp_dd.py:678-693); rows 6i..6i+5
-        // The six rows are read agent block by agent block (18 16-byte loads in flight per block, rows
-        // and blocks 48-byte aligned), each row's sum kept in the original order c = 0 .. 6n-1.
-        const double* Hi = a.dHinv + (size_t)sc * N6 * N6 + (size_t)(6 * i) * N6;
-        double stp[6] = {0, 0, 0, 0, 0, 0};
-        for (int k = 0; k < n; ++k) {
-          dat_d2 h[6][3];
-#pragma unroll
-          for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) h[r][j] = *(const dat_d2*)(Hi + (size_t)r * N6 + 6 * k + 2 * j);
-          const double* e = L.E + (ls * n + k) * DD_ES;
-          double ev[6];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) ev[j] = e[j];
-#pragma unroll
-          for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-              stp[r] += h[r][j].x * ev[2 * j];
-              stp[r] += h[r][j].y * ev[2 * j + 1];
-            }
-        }
-        for (int c = 0; c < 3; ++c) {
-          lF[3 * i + c] += stp[c];
-          lM[3 * i + c] += stp[3 + c];
-        }
+        dd_dual_ascent(a.dHinv + (size_t)sc * N6 * N6 + (size_t)(6 * i) * N6, N6, Es, DD_ES, n, lF + 3 * i, lM + 3 * i);
       } else {
         // the scenario stopped: write its outputs and free the slot
         for (int c = 0; c < 3; ++c) {
@@ -1506,9 +1329,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
           // lambda_F, lambda_M and previous solutions it leaves (control/rqp_dd.py:695-700)
           ++kstep;
           iter = 0;
-#if DAT_DD_WARM
           wrl[0] = 0.0;
-#endif
           qstat = ST_OPTIMAL;
           if (i == 0) {
             build_shared(S, prm, n, a.state + (size_t)sc * a.S, a.acc + ((size_t)kstep * a.B + sc) * 6,
@@ -2135,7 +1956,7 @@ struct dat_handle {
   X(erows, 4 * DAT_NENV * (n)) X(emask, n) X(wrec, (n) * WREC_SIZE) X(best, (n) * BEST_REC)
 #define DAT_ARRAYS_DD(X, n)                                     \
   X(need, 1) X(ipmx, 1) X(slist, 1) X(dHinv, 36 * (n) * (n))    \
-  X(wrec, DAT_DD_WARM ? (n) * WREC_SIZE : 0) X(best, (n) * BEST_REC)
+  X(wrec, (n) * WREC_SIZE) X(best, (n) * BEST_REC)
 #define DAT_ARRAYS_CENT(X, n) X(best, NMAX_CENT * BEST_REC)
 // Both lists of `mode` (a run-time value) through the caller's DAT_ARR(array, elements per scenario), a statement
 #define DAT_ARR_CK(arr, words, off) DAT_ARR(arr, words)

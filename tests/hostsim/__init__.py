@@ -13,7 +13,7 @@ CORE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "distributed_aerial_
 
 def build(force=False):
     deps = [SRC] + [os.path.join(CORE, f)
-                    for f in ("dat_core.hpp", "dat_qp.hpp", "dat_cadmm_step.hpp", "dat_layout.h")]
+                    for f in ("dat_core.hpp", "dat_qp.hpp", "dat_cadmm_step.hpp", "dat_dd_step.hpp", "dat_layout.h")]
     if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950",
                                SRC, "-o", LIB])
@@ -116,6 +116,49 @@ def qp_dd(prm, n, st, acc, lhs, rhs, i, c9):
     status = lib().hs_qp_dd(p(prm), n, p(st), p(acc), p(lhs), p(rhs), lhs.shape[0], i, p(c9), x.ctypes.data_as(D),
                             ctypes.byref(it))
     return x, status, it.value
+
+
+def dd_setup(prm, n, st):
+    """H^-1 of one scenario's DD quasi-Newton matrix (6n x 6n), in k_dd_setup's element order (hs_dd_setup)"""
+    Hinv = np.zeros((6 * n, 6 * n))
+    lib().hs_dd_setup(p(prm), n, p(st), Hinv.ctypes.data_as(D))
+    return Hinv
+
+
+class DDStep:
+    """one DD control step of the host build: f_des (3, n), iters, err_seq (iters - 1), qp_status (n), ipmx"""
+
+    def __init__(self, f_des, iters, err_seq, qp_status, ipmx):
+        self.f_des, self.iters, self.err_seq, self.qp_status, self.ipmx = f_des, iters, err_seq, qp_status, ipmx
+
+
+def dd_warm(prm, n):
+    """a DD controller's warm state before its first step (hs_dd_warm_reset): lamF, lamM (3n), prev (n, 9)"""
+    warm = np.zeros(3 * n), np.zeros(3 * n), np.zeros((n, 9))
+    lib().hs_dd_warm_reset(p(prm), n, *(a.ctypes.data_as(D) for a in warm))
+    return warm
+
+
+def dd_step(prm, n, st, acc, warm, trees=None, res_tol=1e-2, max_iter=100, qp_tol=1e-10):
+    """hs_dd_step: one whole DD control step of one scenario in k_dd's sequence.  warm = (lamF, lamM, prev), float64
+    C-contiguous arrays updated in place (the controller's state from step to step); trees (T, 3) are sorted by x
+    here, as dat_set_forests sorts each forest."""
+    lamF, lamM, prev = warm
+    for a, size in ((lamF, 3 * n), (lamM, 3 * n), (prev, 9 * n)):
+        assert a.dtype == np.float64 and a.flags.c_contiguous and a.size == size
+    nt = 0 if trees is None else len(trees)
+    if nt:
+        trees = np.asarray(trees, dtype=np.float64)
+        trees = np.ascontiguousarray(trees[np.argsort(trees[:, 0], kind="stable")])
+    f = np.zeros((n, 3))
+    err = np.zeros(max_iter + 1)
+    qs = np.zeros(n, dtype=np.int32)
+    ipmx = ctypes.c_int()
+    it = lib().hs_dd_step(p(prm), n, p(st), p(acc), p(trees) if nt else None, nt, ctypes.c_double(res_tol),
+                          int(max_iter), ctypes.c_double(qp_tol), lamF.ctypes.data_as(D), lamM.ctypes.data_as(D),
+                          prev.ctypes.data_as(D), f.ctypes.data_as(D), err.ctypes.data_as(D), qs.ctypes.data_as(I),
+                          ctypes.byref(ipmx))
+    return DDStep(f.T.copy(), it, err[: it - 1].copy(), qs, ipmx.value)
 
 
 def qp_cent(prm, n, st, acc, lhs, rhs):

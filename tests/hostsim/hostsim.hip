@@ -4,7 +4,10 @@
 // the product package): it runs the exact __host__ __device__ code of one GPU lane on the CPU so
 // the reduced-QP algebra, the env rows and the rollout can be checked against the oracle in the
 // dev container, which has no GPU.  The product path has no CPU fallback.
+#include <vector>
+
 #include "../../distributed_aerial_transportation_amd/csrc/dat_cadmm_step.hpp"
+#include "../../distributed_aerial_transportation_amd/csrc/dat_dd_step.hpp"
 
 using namespace dat;
 
@@ -172,6 +175,112 @@ int hs_qp_dd(const double* prm, int n, const double* st, const double* acc, cons
   for (int c = 0; c < 6; ++c) x_out[3 + c] = w[c];
   *iters = o.iters;
   return o.status;
+}
+
+// H^-1 of one scenario's DD quasi-Newton matrix (N x N row-major, N = 6n), as k_dd_setup computes it: the
+// header's element steps (dat_dd_step.hpp) in the serial order the kernel's lanes reproduce
+void hs_dd_setup(const double* prm, int n, const double* st, double* Hinv) {
+  const int N = 6 * n;
+  std::vector<double> Qi(81 * n), Rts(9 * n), H(2 * N * N), fac(N);
+  for (int j = 0; j < n; ++j) {
+    double Q[81], A[162], colk[9];
+    dd_strong_convexity(prm, n, st, j, Q);
+    dd_qinv_augment(Q, A);
+    make_Rt(prm + DAT_P_RCOM(n) + 3 * j, st + DAT_S_RL(n), Rts.data() + 9 * j);
+    for (int k = 0; k < 9; ++k) {
+      const int p = dd_qinv_pivot_row(A, k);
+      for (int c = 0; c < 18; ++c) dd_qinv_exchange(A, k, p, c);
+      for (int r = 0; r < 9; ++r) colk[r] = A[18 * r + k];
+      for (int c = 0; c < 18; ++c) dd_qinv_update_col(A, colk, k, c);
+    }
+    for (int r = 0; r < 9; ++r)
+      for (int c = 0; c < 9; ++c) Qi[81 * j + 9 * r + c] = dd_qinv_sym(A, r, c);
+  }
+  for (int r = 0; r < N; ++r)
+    for (int c = 0; c < N; ++c) {
+      H[2 * N * r + c] = dd_h_element(Qi.data(), Rts.data(), n, r, c);
+      H[2 * N * r + N + c] = (r == c) ? 1.0 : 0.0;
+    }
+  for (int k = 0; k < N; ++k) {
+    const double piv = H[2 * N * k + k];
+    for (int r = 0; r < N; ++r) fac[r] = H[2 * N * r + k];
+    for (int c = 0; c < 2 * N; ++c) dd_hinv_update_col(H.data(), 2 * N, N, fac.data(), piv, k, c);
+  }
+  for (int r = 0; r < N; ++r)
+    for (int c = 0; c < N; ++c) Hinv[N * r + c] = H[2 * N * r + N + c];
+}
+
+// a DD controller's warm state before its first step, as k_warm sets it (that kernel is not the DD step's and keeps
+// its own lines): zero multipliers, every agent holding dd_fallback over the sum of f_eq
+void hs_dd_warm_reset(const double* prm, int n, double* lamF, double* lamM, double* prev) {
+  const double* feq = prm + DAT_P_FEQ(n);
+  double s3[3] = {0, 0, 0};
+  for (int k = 0; k < n; ++k)
+    for (int c = 0; c < 3; ++c) s3[c] += feq[3 * k + c];
+  for (int c = 0; c < 3 * n; ++c) { lamF[c] = 0.0; lamM[c] = 0.0; }
+  for (int i = 0; i < n; ++i) dd_fallback(prm, n, i, s3, prev + 9 * i);
+}
+
+// One DD control step of one scenario in k_dd's sequence, a loop over the agents where the kernel has lanes: every
+// agent's solve of a pass comes before any write of X (the kernel's barrier).  trees: the scenario's forest sorted
+// by x (ntree x DAT_TREE_STRIDE; ntree = 0: no forest).  In / out: the controller's warm state lamF, lamM (3n) and
+// prev (n x 9).  Out: f_des (3n), err_seq (max_iter + 1, the residuals of the passes that did not stop), the
+// agents' last QP status (n) and the IPM iterations of the slowest agent QP.  Returns the pass count.
+int hs_dd_step(const double* prm, int n, const double* st, const double* acc, const double* trees, int ntree,
+               double res_tol, int max_iter, double qp_tol, double* lamF, double* lamM, double* prev, double* f_des,
+               double* err_seq, int* qstatus, int* ipmx) {
+  const int N6 = 6 * n;
+  std::vector<double> Hbuf((size_t)N6 * N6 + 2), Rts(9 * n), X(9 * n), E(6 * n), wrec((size_t)n * WREC_SIZE, 0.0);
+  std::vector<double> best((size_t)n * best_size(1));
+  double* Hinv = Hbuf.data() + (((size_t)Hbuf.data() & 15) ? 1 : 0);  // 16-byte aligned (dd_dual_ascent reads pairs)
+  hs_dd_setup(prm, n, st, Hinv);
+  const double* Rl = st + DAT_S_RL(n);
+  QPShared S;
+  build_shared(S, prm, n, st, acc, prm[DAT_P_KFD], prm[DAT_P_KMD], 3, false);
+  std::vector<QPLane<1>> P(n);
+  std::vector<EnvRows> Ev(n);
+  int nr = NBASE;
+  for (int i = 0; i < n; ++i) {
+    make_Rt(prm + DAT_P_RCOM(n) + 3 * i, Rl, Rts.data() + 9 * i);
+    for (int c = 0; c < 9; ++c) X[9 * i + c] = prev[9 * i + c];  // the controller's current (f, F, M)
+    qstatus[i] = ST_OPTIMAL;
+    lane_dd_static(P[i], prm, i);
+    if (ntree > 0) {  // k_dd<true>
+      double lhs[DAT_NENV][3], rhs[DAT_NENV];
+      unsigned emask;
+      env_rows(prm, n, st, trees, ntree, i, prm[DAT_P_AENVD], &emask, lhs, rhs);
+      set_env_rows(P[i], Ev[i], S, emask, lhs, rhs);
+    }
+    nr = nr > rows_needed(P[i].emask) ? nr : rows_needed(P[i].emask);
+  }
+  int iter = 0;
+  *ipmx = 0;
+  for (;;) {
+    for (int i = 0; i < n; ++i) {
+      double c9[9], y[1][3], w[6];
+      dd_prices(prm, n, i, lamF, lamM, Rl, c9);
+      set_dd_price(P[i], prm, n, i, c9);
+      const IPMOut o = ipm_solve_rows<MODE_DD, 1, IPM_FAST, true>(
+          nr, PlainRef<QPShared>{&S}, EnvPlain{&Ev[i]}, RtPtr{Rts.data() + 9 * i}, P[i], prm + DAT_P_FEQ(n) + 3 * i, y,
+          w, best.data() + (size_t)i * best_size(1), 50, qp_tol, wrec.data() + (size_t)i * WREC_SIZE,
+          dd_warm_pass(iter));
+      diag(o);
+      *ipmx = *ipmx > o.iters ? *ipmx : o.iters;
+      qstatus[i] = o.status;
+      dd_take_solve(o.status, y[0], w, prm, n, i, X.data(), prev + 9 * i);
+    }
+    for (int c = 0; c < 9 * n; ++c) X[c] = prev[c];
+    ++iter;
+    for (int i = 0; i < n; ++i) dd_consensus_error(X.data(), Rts.data(), 9, n, i, E.data() + 6 * i);
+    const double res = dd_pass_residual(E.data(), 6, n);
+    if (dd_stop(res, res_tol, iter, max_iter)) break;
+    err_seq[iter - 1] = res;
+    for (int i = 0; i < n; ++i)
+      dd_dual_ascent(Hinv + (size_t)(6 * i) * N6, N6, E.data(), 6, n, lamF + 3 * i, lamM + 3 * i);
+  }
+  for (int i = 0; i < n; ++i)
+    for (int c = 0; c < 3; ++c) f_des[3 * i + c] = X[9 * i + c];
+  return iter;
 }
 
 int hs_qp_cent(const double* prm, int n, const double* st, const double* acc, const double* env_lhs,

@@ -13,23 +13,9 @@ from oracle import forest as of
 from oracle import model as om
 from oracle import scenarios as osc
 from tests._golden import load, state_from, unpack_flat
+from tests._tolerances import DD_ERR_RTOL, ERR_ATOL, ERR_RTOL, REL, _ambiguous  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-REL = 1e-5
-# Residual sequences (err_seq) are consensus errors F_i - sum_j f_j: differences of forces of order
-# m_T g (17-30 N) that shrink to ~1e-2, so they inherit the agent-QP solution error amplified by that
-# cancellation.  tools/dd_sensitivity.py runs the ORACLE against itself on the DD step test's
-# scenarios: IPM tolerance 1e-10 vs 1e-11 moves err_seq by up to 9.6e-5 relative (1.3e-6 N
-# absolute at err ~ 1e-2), 1e-12 vs 1e-11 by 1.6e-5, while an explicit H^-1 instead of cho_solve
-# moves it by 2e-11.  The comparison is therefore rtol 1e-4 OR 2e-6 N absolute (1e-7 of m_T g).
-ERR_RTOL, ERR_ATOL = 1e-4, 2e-6
-# DD err_seq by team size where the oracle's own sensitivity is larger (tools/dd_sensitivity.py n: IPM
-# tolerance 1e-11 -> 1e-10 moves the oracle's err_seq by 1.05e-2 relative at n = 4, 7.7e-4 at n = 11
-# and 5.7e-3 at n = 16 -- those teams' agent QPs are strongly convex only through the 1e-6
-# regularisation in some directions, so the solution moves ~tol / 1e-6 -- against 4.3e-5 at n = 3,
-# 9.6e-5 at n = 6 and 2.7e-5 at n = 8): 3x the measured change.
-DD_ERR_RTOL = {4: 3e-2, 11: 2.5e-3, 16: 1.8e-2}
 
 
 def _eng(mode, n, B, **kw):
@@ -133,17 +119,11 @@ def test_gpu_cadmm_default_tolerance_golden():
         assert _rel(r.f_des[0], d["tol_f"][k]) < REL
 
 
-def _ambiguous(seq, tol=1e-2, band=1e-7):
-    """The reference stops when err < tol; a residual within `band` (relative) of tol can flip the count
-    (such scenarios are excluded from exact-count checks, and tests assert they are rare)."""
-    return any(abs(e - tol) < band * tol for e in seq)
-
-
-@pytest.mark.parametrize("n", [3, 4, 6, 8, 11, 16])
+@pytest.mark.parametrize("n", [3, 4, 6, 8, 9, 11, 16])
 def test_gpu_dd_step_matches_oracle(n):
     """DD control step (control/rqp_dd.py:695-752) incl. the warm multipliers of a second step:
     iteration counts exact, f_des within 1e-5, residual sequences within 1e-4 relative.  n <= 8 runs
-    k_dd_setup<n> (H columns in registers), n = 11 and 16 the LDS path (k_dd_setup<0>, > 64 KB LDS)."""
+    k_dd_setup<n> (H columns in registers), n = 9, 11 and 16 the LDS path (k_dd_setup<0>, > 64 KB LDS)."""
     from distributed_aerial_transportation_amd import scenarios
 
     B = 6
@@ -426,3 +406,45 @@ def test_gpu_dd_persistent_drain():
             continue
         assert r1.iters[b] == st1.iter and r2.iters[b] == st2.iter, (b, r1.iters[b], st1.iter, r2.iters[b], st2.iter)
         assert _rel(r1.f_des[b], f1) < REL and _rel(r2.f_des[b], f2) < REL
+
+
+@pytest.mark.parametrize("n,B,forest", [(3, 22, False), (8, 9, False), (9, 8, False), (3, 22, True)])
+def test_gpu_dd_step_matches_host_step(n, B, forest):
+    """k_dd_setup / k_dd against the host build of the same step rules (dat_dd_step.hpp, tests/hostsim hs_dd_step),
+    two steps each (warm multipliers): iteration counts exact, f_des within 1e-5, residual sequences within
+    ERR_RTOL / ERR_ATOL (the host fuses no multiply-adds, so the match is not bitwise).  One scenario more than the
+    G = floor(64 / n) slots of a workgroup, so every shape refills a slot: n = 3 (G = 21), n = 8 (the register
+    path's two columns per lane), n = 9 (the smallest team of the LDS path), and n = 3 in a forest whose trees put
+    env rows on some agents (k_dd<true>)."""
+    from distributed_aerial_transportation_amd import scenarios
+    from tests import hostsim as hs
+
+    prm = scenarios.params_block(n)
+    rng = np.random.default_rng(900 + 10 * n + forest)
+    eng = _eng("dd", n, B, record_err=True)
+    eng.set_persistent_blocks(1)
+    trees = None
+    if forest:
+        from tests import _envscenes as es
+        from tests.test_gpu_env_rows_reference import _forest
+
+        cases = es.battery(n)[0]
+        trees = next(c for c in cases if c.name == "crowd").trees
+        states = np.stack([c.state for c in cases[:B]])
+        eng.set_forests([_forest(trees)])
+        rows = sum(len(hs.env_rows(prm, n, x, trees, i, es.ALPHA_D)[1]) for x in states for i in range(n))
+        assert rows > 0
+        acc = np.concatenate([rng.uniform(-1, 1, (B, 3)), np.zeros((B, 3))], axis=1)
+    else:
+        states = scenarios.perturbed_states(n, B, rng)
+        acc = np.concatenate([rng.uniform(-3, 3, (B, 3)), rng.uniform(-3, 3, (B, 3))], axis=1)
+    r1 = eng.control(states, acc)
+    r2 = eng.control(states, acc[::-1].copy())
+    for b in range(B):
+        warm = hs.dd_warm(prm, n)
+        for r, a in ((r1, acc[b]), (r2, acc[B - 1 - b])):
+            h = hs.dd_step(prm, n, states[b], a, warm, trees)
+            assert r.iters[b] == h.iters, (b, r.iters[b], h.iters)
+            assert _rel(r.f_des[b], h.f_des) < REL, (b, _rel(r.f_des[b], h.f_des))
+            np.testing.assert_allclose(r.err_seq[b, : h.iters - 1], h.err_seq, rtol=ERR_RTOL, atol=ERR_ATOL)
+            assert np.array_equal(r.qp_status[b], h.qp_status), (b, r.qp_status[b], h.qp_status)

@@ -11,6 +11,8 @@ from oracle.ipm import OPTIMAL, solve_qp
 from tests import hostsim as hs
 from tests.hostsim import TAIL_PASS, TAIL_PREV
 from tests._golden import load, state_from
+from tests._tolerances import DD_ERR_RTOL, ERR_ATOL, ERR_RTOL, REL, _ambiguous
+from tests.test_gpu_parity import _ostate, _rel
 
 
 def _rand_state(rng, n):
@@ -282,3 +284,89 @@ def test_loose_caps_solved_within_clarabel_tol():
         assert not inb or hs.last_diag()[0] <= 1e-8, (k, hs.last_diag())
         rel, bound = _loose_bound(d, k, f.reshape(n, 3).T)
         assert rel < bound, (k, rel, bound)
+
+
+# ---- the DD step of the host build (tests/hostsim hs_dd_setup, hs_dd_step: the rules of dat_dd_step.hpp in k_dd's
+# sequence), the CPU statement of test_gpu_parity.py's DD checks
+
+
+def test_host_dd_step_golden():
+    """test_gpu_dd_golden on the host step: 25 fixed passes and the default tolerance against the reference's own
+    loop (ref_dd.npz), the warm state carried from step to step."""
+    from distributed_aerial_transportation_amd import scenarios, system
+
+    d = load("ref_dd.npz")
+    prm = _prm(3)
+    x = system.pack_state(scenarios.rest_state(3))
+    warm = hs.dd_warm(prm, 3)
+    for k in range(d["fixed_err"].shape[0]):
+        r = hs.dd_step(prm, 3, x, d["acc"][k], warm, res_tol=0.0, max_iter=25)
+        # converged tails sit at the 1e-14 rounding floor: absolute tolerance 1e-9 there
+        np.testing.assert_allclose(r.err_seq[:25], d["fixed_err"][k], rtol=1e-4, atol=1e-9)
+        assert _rel(r.f_des, d["fixed_f"][k]) < REL
+    warm = hs.dd_warm(prm, 3)
+    for k in range(d["tol_iters"].shape[0]):
+        r = hs.dd_step(prm, 3, x, d["acc"][k], warm)
+        assert r.iters == d["tol_iters"][k]
+        assert _rel(r.f_des, d["tol_f"][k]) < REL
+        it = int(d["tol_iters"][k])
+        np.testing.assert_allclose(r.err_seq[: it - 1], d["tol_err"][k][: it - 1], rtol=ERR_RTOL, atol=ERR_ATOL)
+
+
+@pytest.mark.parametrize("n", [3, 6, 8, 9])
+def test_host_dd_step_matches_oracle(n):
+    """test_gpu_dd_step_matches_oracle on the host step (same scenarios, seeds, two-step pattern and assertions):
+    iteration counts exact, f_des within 1e-5, residual sequences within the team size's tolerance.  The oracle
+    alone decides which scenarios are ambiguous, and at most one of the six may be (two where the team size has
+    its own tolerance)."""
+    from distributed_aerial_transportation_amd import scenarios
+    from oracle import controllers as oc
+
+    B = 6
+    rng = np.random.default_rng(10 + n)
+    states = scenarios.perturbed_states(n, B, rng)
+    acc = np.concatenate([rng.uniform(-3, 3, (B, 3)), rng.uniform(-3, 3, (B, 3))], axis=1)
+    prm = _prm(n)
+    skipped = 0
+    for b in range(B):
+        warm = hs.dd_warm(prm, n)
+        r1 = hs.dd_step(prm, n, states[b], acc[b], warm)
+        r2 = hs.dd_step(prm, n, states[b], acc[B - 1 - b], warm)
+        ctl = oc.DD(osc.params(n), osc.col_radius(n))
+        s = _ostate(states[b], n)
+        f1, st1 = ctl.control(s, (acc[b, :3], acc[b, 3:]))
+        f2, st2 = ctl.control(s, (acc[B - 1 - b, :3], acc[B - 1 - b, 3:]))
+        rtol = DD_ERR_RTOL.get(n, ERR_RTOL)
+        band = rtol / 3 if n in DD_ERR_RTOL else 1e-7  # the measured sensitivity itself
+        if _ambiguous(st1.err_seq, band=band) or _ambiguous(st2.err_seq, band=band):
+            skipped += 1
+            continue
+        assert r1.iters == st1.iter and r2.iters == st2.iter, (b, r1.iters, st1.iter, r2.iters, st2.iter)
+        assert _rel(r1.f_des, f1) < REL and _rel(r2.f_des, f2) < REL, (_rel(r1.f_des, f1), _rel(r2.f_des, f2))
+        np.testing.assert_allclose(r1.err_seq, st1.err_seq, rtol=rtol, atol=ERR_ATOL)
+        np.testing.assert_allclose(r2.err_seq, st2.err_seq, rtol=rtol, atol=ERR_ATOL)
+        assert np.all(r1.qp_status == 0) and np.all(r2.qp_status == 0)
+    assert skipped <= (2 if n in DD_ERR_RTOL else 1)
+
+
+@pytest.mark.parametrize("n", [3, 8, 9])
+def test_host_dd_setup_matches_oracle_inverse(n):
+    """hs_dd_setup (Q_i^-1 and H^-1 by the kernels' Gauss-Jordan eliminations) against np.linalg.inv of the oracle's
+    quasi-Newton matrix, entries relative to the largest of the inverse.  The bound is the oracle's own: 10 x the
+    spread between np.linalg.inv and cho_solve (what the oracle's step uses) on the same six matrices, for the
+    different elimination order.  Measured: spread 5.4e-16 / 7.0e-16 / 7.4e-16 at n = 3 / 8 / 9 (condition numbers
+    38 / 118 / 140), the host build 4.3e-15 / 7.0e-16 / 9.2e-16 off."""
+    import scipy.linalg as sl
+    from distributed_aerial_transportation_amd import scenarios
+    from oracle import controllers as oc
+
+    states = scenarios.perturbed_states(n, 6, np.random.default_rng(10 + n))
+    spread = dev = 0.0
+    for x in states:
+        _, H = oc.DD(osc.params(n), osc.col_radius(n)).qn_matrix(_ostate(x, n))
+        Hi = np.linalg.inv(H)
+        scale = np.max(np.abs(Hi))
+        spread = max(spread, np.max(np.abs(sl.cho_solve(sl.cho_factor(H), np.eye(6 * n)) - Hi)) / scale)
+        dev = max(dev, np.max(np.abs(hs.dd_setup(_prm(n), n, x) - Hi)) / scale)
+    assert 0.0 < spread < 1e-14
+    assert dev < 10.0 * spread, (dev, spread)
