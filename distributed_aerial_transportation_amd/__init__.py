@@ -18,4 +18,9 @@ def __getattr__(name):
         from . import control
 
         return getattr(control, name)
+    if name == "pmrl" or name.startswith("PMRL") or name in ("pack_pmrl_params", "pack_pmrl_state", "unpack_pmrl_state"):
+        import importlib
+
+        mod = importlib.import_module(".pmrl", __name__)  # (PMRLDynamics loads libdat.so on use)
+        return mod if name == "pmrl" else getattr(mod, name)
     raise AttributeError(name)

@@ -28,7 +28,7 @@ OBJ_DIR = os.path.join(PKG, "build")
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on"]
 DEPS = [SRC, SRC_CENT, SRC_COMM, os.path.join(PKG, "csrc", "dat_core.hpp"), os.path.join(PKG, "csrc", "dat_qp.hpp"),
         os.path.join(PKG, "csrc", "dat_cadmm_step.hpp"), os.path.join(PKG, "csrc", "dat_dd_step.hpp"),
-        os.path.join(PKG, "csrc", "dat_kargs.hpp"),
+        os.path.join(PKG, "csrc", "dat_pmrl_step.hpp"), os.path.join(PKG, "csrc", "dat_kargs.hpp"),
         os.path.join(PKG, "csrc", "dat_ckpt.hpp"),
         os.path.join(PKG, "csrc", "dat_layout.h"), os.path.join(REPO, "include", "dat.h")]
 
@@ -189,6 +189,8 @@ EXPORTS = {
     "dat_get_collision_stats": (ctypes.c_int, [H, LL, D]),
     "dat_get_agent_qp_ms": (ctypes.c_int, [H, D]),
     "dat_rp_rollout": (ctypes.c_int, [H, ctypes.c_int, D]),
+    "dat_pmrl_rollout": (ctypes.c_int, [H, ctypes.c_int, D, ctypes.c_int]),
+    "dat_pmrl_forward": (ctypes.c_int, [H, D, D, D, D, D]),
     "dat_low_level_control": (ctypes.c_int, [H, D, D, D]),
     "dat_log_begin": (ctypes.c_int, [H, I, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dat_log_counts": (ctypes.c_int, [H, LL, LL, LL]),

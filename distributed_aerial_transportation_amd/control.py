@@ -349,6 +349,27 @@ class BatchedController:
             fd = L.f64(np.asarray(f).transpose(0, 2, 1).reshape(self.batch, 3 * self.n))
         L.check(self._lib.dat_rp_rollout(self._h, int(steps), L.ptr(fd)))
 
+    def pmrl_rollout(self, steps: int, f: np.ndarray) -> None:
+        """Point-mass rigid-link dynamics (dat_pmrl_rollout): `steps` steps under the force schedule f, (B, 3, n)
+        held throughout or (nf, B, 3, n) with steps % nf == 0 and each set held steps / nf steps."""
+        f = np.asarray(f, float)
+        if f.ndim == 3:
+            f = f[None]
+        assert f.ndim == 4 and f.shape[1:] == (self.batch, 3, self.n), f.shape
+        fd = L.f64(f.transpose(0, 1, 3, 2).reshape(f.shape[0], self.batch, 3 * self.n))
+        L.check(self._lib.dat_pmrl_rollout(self._h, int(steps), L.ptr(fd), int(f.shape[0])))
+
+    def pmrl_forward(self, f: np.ndarray):
+        """PMRLDynamics.forward_dynamics at the current states (dat_pmrl_forward) under the thrusts f (B, 3, n):
+        ((ddq (B, 3, n), dvl (B, 3), dwl (B, 3)), T (B, n)).  The states are left alone."""
+        B, n = self.batch, self.n
+        f = np.asarray(f, float)
+        assert f.shape == (B, 3, n), f.shape
+        fd = L.f64(f.transpose(0, 2, 1).reshape(B, 3 * n))
+        ddq, dvl, dwl, T = np.empty((B, n, 3)), np.empty((B, 3)), np.empty((B, 3)), np.empty((B, n))
+        L.check(self._lib.dat_pmrl_forward(self._h, L.ptr(fd), L.ptr(ddq), L.ptr(dvl), L.ptr(dwl), L.ptr(T)))
+        return (ddq.transpose(0, 2, 1).copy(), dvl, dwl), T
+
     def set_sub_batches(self, count: int) -> None:
         """dat_set_sub_batches: closed_loop on `count` sub-batches with one stream each (C-ADMM)."""
         L.check(self._lib.dat_set_sub_batches(self._h, int(count)))
@@ -405,8 +426,8 @@ class BatchedController:
         an HL record per control step and a step record at every simulation step i with i % log_every == 0
         (log_every: the reference's log_freq, default hl_every), and with summary=True the per-step iters,
         min_env_dist and collision of all scenarios.  The buffers hold hl_capacity HL steps; a closed_loop call
-        that would pass it raises DatError (log_read, log_clear, then go on).  control, control_steps, rollout
-        and rp_rollout are not recorded."""
+        that would pass it raises DatError (log_read, log_clear, then go on).  control, control_steps, rollout,
+        rp_rollout, pmrl_rollout and pmrl_forward are not recorded."""
         if scenarios is None:
             sc, count = None, self.batch
         else:

@@ -13,6 +13,9 @@
 //              (control/rqp_centralized.py:436-448): dat_cent.hip.
 //   k_rollout_agents  low-level SO(3) law + dynamics + Lie integration, one lane per agent.
 //   k_desired  forest desired-acceleration law (example/rqp_example.py:33-59).
+//   k_pmrl_rollout, k_pmrl_forward  point-mass rigid-link system (system/point_mass_rigid_link.py:135-254), one
+//              lane per link, the link tensions from a 6 x 6 system replicated on the scenario's lanes
+//              (dat_pmrl_step.hpp).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -31,6 +34,7 @@
 #include "dat_ckpt.hpp"
 #include "dat_kargs.hpp"
 #include "dat_dd_step.hpp"
+#include "dat_pmrl_step.hpp"
 
 using namespace dat;
 
@@ -1573,6 +1577,134 @@ __global__ void k_rp_rollout(KArgs a, int steps, double dt, const double* f) {
   a.counter[sc] = cnt;
 }
 
+// Point-mass rigid-link system (PMRLDynamics, system/point_mass_rigid_link.py:135-254; the pieces of
+// dat_pmrl_step.hpp), k_rollout_agents' mapping: one lane per link, G = floor(64/n) scenarios per 64-lane block, idle
+// lanes masked.  A lane holds its link (q, dq) and a copy of the payload in registers across the steps.  Per step one
+// LDS exchange between one pair of barriers: lane i publishes (m_i, y_i, g_i); every lane of the scenario assembles
+// S and G y from the records in link order (identical bits in all of them), solves the 6 x 6 system and integrates
+// its own link and its copy of the payload.  Lane 0 of a scenario writes the payload and the counter back.
+constexpr int PM_X = 8;  // per lane in LDS: m, y, g (6)
+// the accelerations at the lane's state: the lane's T and ddq, the scenario's dvl and dwl (all lanes of a block
+// call it, valid or not: it holds the step's two barriers)
+__device__ __forceinline__ void pmrl_lane_forward(const double* prm, int n, int i, bool valid, double* mine,
+                                                  const double* grp, const double* Rl, const double* wl,
+                                                  const double* q, const double* dq, const double* f, double* T,
+                                                  double* ddq, double* dvl, double* dwl) {
+  PmrlPayload p;
+  PmrlLink lk;
+  if (valid) {
+    pmrl_payload_terms(prm, Rl, wl, p);
+    pmrl_link_terms(prm, n, i, p, Rl, q, dq, f, lk);
+    mine[0] = prm[DAT_P_PM_M(n) + i];
+    mine[1] = lk.y;
+    for (int c = 0; c < 6; ++c) mine[2 + c] = lk.g[c];
+  }
+  __syncthreads();
+  if (valid) {
+    double S[21], z[6];
+    pmrl_system_clear(S, z);
+    for (int k = 0; k < n; ++k) {
+      double rec[PM_X];
+      for (int c = 0; c < PM_X; ++c) rec[c] = grp[k * PM_X + c];
+      pmrl_system_add(S, z, rec[0], rec[1], rec + 2);
+    }
+    pmrl_solve6(S, z);
+    PmrlSums s;
+    pmrl_payload_accel(prm, n, p, z, s, dvl, dwl);
+    *T = pmrl_tension(prm[DAT_P_PM_M(n) + i], lk.y, lk.g, z);
+    pmrl_link_accel(prm, n, i, Rl, lk, q, *T, s, ddq);
+  }
+  __syncthreads();  // the records are read before the next step overwrites them
+}
+// `steps` steps of dt under the force schedule f[nf][B][3n] (agent-major): step s uses set s / (steps / nf)
+__global__ __launch_bounds__(64) void k_pmrl_rollout(KArgs a, int steps, int nf, double dt, const double* f) {
+  __shared__ double xs[64 * PM_X];
+  const int n = a.n, G = 64 / n, NT = G * n;
+  const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
+  const int sc = blockIdx.x * G + ls;
+  const bool valid = lane < NT && sc < a.B;
+  const double* prm = valid ? prm_of(a, sc) : a.params;
+  double* g = valid ? a.state + (size_t)sc * a.S : nullptr;
+  double q[3] = {0, 0, 1}, dq[3] = {0, 0, 0}, xl[3], vl[3], Rl[9], wl[3], fi[3] = {0, 0, 0};
+  int cnt = 0;
+  if (valid) {
+    for (int c = 0; c < 3; ++c) {
+      q[c] = g[DAT_S_Q(n) + 3 * i + c];
+      dq[c] = g[DAT_S_DQ(n) + 3 * i + c];
+      xl[c] = g[DAT_S_XL(n) + c];
+      vl[c] = g[DAT_S_VL(n) + c];
+      wl[c] = g[DAT_S_WL(n) + c];
+    }
+    for (int k = 0; k < 9; ++k) Rl[k] = g[DAT_S_RL(n) + k];
+    cnt = a.counter[sc];
+  }
+  const int hold = steps / nf;  // steps a force set is held
+  const size_t fset = (size_t)a.B * 3 * n;
+  const double* fp = f + (valid ? (size_t)sc * 3 * n + 3 * i : 0);
+  for (int s = 0, left = 0; s < steps; ++s, --left) {
+    if (left == 0) {
+      left = hold;
+      if (valid)
+        for (int c = 0; c < 3; ++c) fi[c] = fp[c];
+      fp += fset;
+    }
+    double T, ddq[3], dvl[3], dwl[3];
+    pmrl_lane_forward(prm, n, i, valid, xs + lane * PM_X, xs + ls * n * PM_X, Rl, wl, q, dq, fi, &T, ddq, dvl, dwl);
+    if (valid) {
+      pmrl_integrate_link(q, dq, ddq, dt);
+      pmrl_integrate_payload(xl, vl, Rl, wl, dvl, dwl, dt, &cnt);
+    }
+  }
+  if (valid) {
+    for (int c = 0; c < 3; ++c) {
+      g[DAT_S_Q(n) + 3 * i + c] = q[c];
+      g[DAT_S_DQ(n) + 3 * i + c] = dq[c];
+    }
+    if (i == 0) {
+      for (int c = 0; c < 3; ++c) {
+        g[DAT_S_XL(n) + c] = xl[c];
+        g[DAT_S_VL(n) + c] = vl[c];
+        g[DAT_S_WL(n) + c] = wl[c];
+      }
+      for (int k = 0; k < 9; ++k) g[DAT_S_RL(n) + k] = Rl[k];
+      a.counter[sc] = cnt;
+    }
+  }
+}
+// PMRLDynamics.forward_dynamics (:156-208) at the current states, which it leaves alone: ddq (B x 3n, agent-major),
+// dvl, dwl (B x 3), T (B x n) under the thrusts f (B x 3n)
+__global__ __launch_bounds__(64) void k_pmrl_forward(KArgs a, const double* f, double* ddq_o, double* dvl_o,
+                                                     double* dwl_o, double* T_o) {
+  __shared__ double xs[64 * PM_X];
+  const int n = a.n, G = 64 / n, NT = G * n;
+  const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
+  const int sc = blockIdx.x * G + ls;
+  const bool valid = lane < NT && sc < a.B;
+  const double* prm = valid ? prm_of(a, sc) : a.params;
+  const double* g = valid ? a.state + (size_t)sc * a.S : nullptr;
+  double q[3] = {0, 0, 1}, dq[3] = {0, 0, 0}, Rl[9], wl[3], fi[3] = {0, 0, 0};
+  if (valid) {
+    for (int c = 0; c < 3; ++c) {
+      q[c] = g[DAT_S_Q(n) + 3 * i + c];
+      dq[c] = g[DAT_S_DQ(n) + 3 * i + c];
+      wl[c] = g[DAT_S_WL(n) + c];
+      fi[c] = f[(size_t)sc * 3 * n + 3 * i + c];
+    }
+    for (int k = 0; k < 9; ++k) Rl[k] = g[DAT_S_RL(n) + k];
+  }
+  double T, ddq[3], dvl[3], dwl[3];
+  pmrl_lane_forward(prm, n, i, valid, xs + lane * PM_X, xs + ls * n * PM_X, Rl, wl, q, dq, fi, &T, ddq, dvl, dwl);
+  if (valid) {
+    for (int c = 0; c < 3; ++c) ddq_o[(size_t)sc * 3 * n + 3 * i + c] = ddq[c];
+    T_o[(size_t)sc * n + i] = T;
+    if (i == 0)
+      for (int c = 0; c < 3; ++c) {
+        dvl_o[(size_t)sc * 3 + c] = dvl[c];
+        dwl_o[(size_t)sc * 3 + c] = dwl[c];
+      }
+  }
+}
+
 template <int ADV>
 __global__ void k_desired(KArgs a, double* acc) {
   const int sc = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1904,6 +2036,8 @@ struct dat_handle {
   std::vector<double> marks;
   double* acc_seq = nullptr;  // dat_control_steps: K x B x 6 desired accelerations (grown on demand)
   size_t acc_seq_cap = 0;
+  double* pmrl_buf = nullptr;  // dat_pmrl_rollout: the force schedule (nf x B x 3n); dat_pmrl_forward: f and its outputs
+  size_t pmrl_cap = 0;         // (grown on demand)
   // C-ADMM closed loop on sub-batches (dat_set_sub_batches): contiguous scenario ranges, each with its own
   // stream, so one sub-batch's kernels fill the drain tail and the short kernels of the others
   int nsub = 1;
@@ -3538,6 +3672,67 @@ int dat_rp_rollout(dat_handle* h, int steps, const double* f) {
   hipLaunchKernelGGL(k_rp_rollout, dim3((B + 63) / 64), dim3(64), 0, h->stream, a, steps, h->cfg.dt,
                      (const double*)h->fdes);
   HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+namespace {
+// the handle's buffer of the PMRL entry points, at least `need` doubles
+int pmrl_reserve(dat_handle* h, size_t need) {
+  if (need <= h->pmrl_cap) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  dfree(h, h->pmrl_buf);
+  h->pmrl_cap = 0;
+  if (dalloc(h, &h->pmrl_buf, need)) return -1;
+  h->pmrl_cap = need;
+  return 0;
+}
+}  // namespace
+
+int dat_pmrl_rollout(dat_handle* h, int steps, const double* f, int nf) {
+  if (!h) return fail("dat_pmrl_rollout: null handle");
+  if (!f) return fail("dat_pmrl_rollout: null force schedule");
+  if (steps < 0) return fail("dat_pmrl_rollout: negative steps");
+  if (nf < 1) return fail("dat_pmrl_rollout: nf must be >= 1");
+  if (steps % nf != 0)
+    return fail("dat_pmrl_rollout: steps (" + std::to_string(steps) + ") must be a multiple of nf (" +
+                std::to_string(nf) + ")");
+  if (!h->have_params) return fail("dat_pmrl_rollout: params not set");
+  if (steps == 0) return 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int B = h->cfg.batch, n = h->cfg.n;
+  const size_t words = (size_t)nf * B * 3 * n;
+  if (pmrl_reserve(h, words)) return -1;
+  HIPCHK(hipMemcpyAsync(h->pmrl_buf, f, sizeof(double) * words, hipMemcpyHostToDevice, h->stream));
+  KArgs a = kargs(h);
+  const int G = 64 / n;
+  hipLaunchKernelGGL(k_pmrl_rollout, dim3((B + G - 1) / G), dim3(64), 0, h->stream, a, steps, nf, h->cfg.dt,
+                     (const double*)h->pmrl_buf);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dat_pmrl_forward(dat_handle* h, const double* f, double* ddq, double* dvl, double* dwl, double* T) {
+  if (!h) return fail("dat_pmrl_forward: null handle");
+  if (!f || !ddq || !dvl || !dwl || !T) return fail("dat_pmrl_forward: null argument");
+  if (!h->have_params) return fail("dat_pmrl_forward: params not set");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int B = h->cfg.batch, n = h->cfg.n;
+  // f, ddq (3n each), T (n), dvl, dwl (3 each) per scenario, one after the other
+  const size_t of = 0, oq = (size_t)B * 3 * n, oT = 2 * oq, ov = oT + (size_t)B * n, ow = ov + (size_t)B * 3;
+  if (pmrl_reserve(h, ow + (size_t)B * 3)) return -1;
+  double* d = h->pmrl_buf;
+  HIPCHK(hipMemcpyAsync(d + of, f, sizeof(double) * oq, hipMemcpyHostToDevice, h->stream));
+  KArgs a = kargs(h);
+  const int G = 64 / n;
+  hipLaunchKernelGGL(k_pmrl_forward, dim3((B + G - 1) / G), dim3(64), 0, h->stream, a, (const double*)(d + of), d + oq,
+                     d + ov, d + ow, d + oT);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(ddq, d + oq, sizeof(double) * oq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(T, d + oT, sizeof(double) * B * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(dvl, d + ov, sizeof(double) * B * 3, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(dwl, d + ow, sizeof(double) * B * 3, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

@@ -36,6 +36,14 @@
 #define DAT_P_J(n) (DAT_P_HDR + 9 * (n))         // quad inertias J_i (9n, row-major 3x3 each)
 #define DAT_P_JINV(n) (DAT_P_HDR + 18 * (n))     // J_i^-1 (9n)
 #define DAT_PARAM_SIZE(n) (DAT_P_HDR + 27 * (n))
+// Point-mass rigid-link system (PMRLParameters, reference system/point_mass_rigid_link.py:37-64): ml, Jl, Jl^-1 in
+// MT, JT, JTI and r in R and RCOM, as the rigid payload's block; the system has no actuator inertias, so inside the
+// region DAT_P_J(n) (9n >= 2n + 9 words for n >= 3) lie the robot masses, the link lengths and the upper Cholesky
+// factor U of Jl^-1 (U'U = Jl^-1, :59), row-major 3x3.
+#define DAT_P_PM_M(n) (DAT_P_J(n))                   // m (n)
+#define DAT_P_PM_L(n) (DAT_P_J(n) + (n))             // L (n)
+#define DAT_P_PM_U(n) (DAT_P_J(n) + 2 * (n))         // chol(Jl^-1), upper (9)
+#define DAT_P_PM_END(n) (DAT_P_J(n) + 2 * (n) + 9)   // end of the PMRL words of the region
 
 // ---- state block (one per scenario), size DAT_STATE_SIZE(n) doubles ------------------------------
 // RQPState (reference system/rigid_quadrotor_payload.py:87-119): R_i (9n, row-major 3x3), w_i (3n),
@@ -48,6 +56,11 @@
 #define DAT_S_RL(n) (12 * (n) + 6)
 #define DAT_S_WL(n) (12 * (n) + 15)
 #define DAT_STATE_SIZE(n) (12 * (n) + 18)
+// PMRLState (reference system/point_mass_rigid_link.py:67-132) in the same block: the link directions q_i (3n,
+// agent-major) at the head of the R region, whose other 6n words are zero, their rates dq_i (3n) in the W region;
+// xl, vl, Rl, wl and the int counter where they are.
+#define DAT_S_Q(n) 0
+#define DAT_S_DQ(n) (DAT_S_W(n))
 
 // ---- forest / mountain record (DAT_MOUNTAIN_SIZE doubles) -----------------------------------------
 // example/env_forest.py:22-31,74-77: centre (2), radius, sphere radius, centre depth

@@ -172,6 +172,21 @@ int dat_low_level_control(dat_handle* h, const double* f_des, double* thrust, do
  * the rigid-payload parameter block (rigid_payload.pack_rp_params: mT = ml, JT = Jl, r_com = r), whose
  * centralized QP is RPCentralizedController (control/rp_centralized.py:9-306) via dat_control_step. */
 int dat_rp_rollout(dat_handle* h, int steps, const double* f);
+/* Point-mass rigid-link system: n point-mass robots carry the rigid payload on rigid links.  `steps` calls of
+ * PMRLDynamics.integrate (system/point_mass_rigid_link.py:251-254: forward_dynamics :156-208, then
+ * PMRLState.integrate :113-132 with project_q :101-105 at every step and project_R every 20) in one launch, on
+ * states in the PMRL layout (dat_layout.h: q at DAT_S_Q, dq at DAT_S_DQ, the payload and the counter where they
+ * are) with the PMRL parameter block (pmrl.pack_pmrl_params: ml, Jl, r as the rigid payload's, m, L and
+ * chol(Jl^-1) at DAT_P_PM_*).  f: the force schedule nf x B x 3n (agent-major, ground frame), nf >= 1 and
+ * steps % nf == 0; step s applies set s / (steps / nf), so nf = steps changes the force at every step and nf = 1
+ * holds one set.  The link tensions come from the reduced 6 x 6 system of csrc/dat_pmrl_step.hpp instead of the
+ * reference's n x n solve (:176-198).  A bad argument or missing parameters: an error code, the message in
+ * dat_last_error, nothing launched. */
+int dat_pmrl_rollout(dat_handle* h, int steps, const double* f, int nf);
+/* PMRLDynamics.forward_dynamics (system/point_mass_rigid_link.py:156-208) at the current states, which it leaves
+ * alone: under the thrusts f (B x 3n, agent-major) the accelerations ddq (B x 3n, agent-major), dvl and dwl
+ * (B x 3) and the link tensions T (B x n). */
+int dat_pmrl_forward(dat_handle* h, const double* f, double* ddq, double* dvl, double* dwl, double* T);
 
 /* ---- device-resident closed loop (the loop of example/rqp_example.py:120-131 with the desired
  * acceleration of :33-59): hl_steps x (desired acceleration + control step +
@@ -240,9 +255,9 @@ int dat_get_step_marks(dat_handle* h, double* marks_ms, int max_marks);
  *
  * The log clock counts the simulation steps run by dat_closed_loop since dat_log_begin; every dat_closed_loop
  * call starts at an HL instant, so it is a multiple of hl_every between calls.  dat_control_step,
- * dat_control_steps, dat_rollout and dat_rp_rollout are NOT recorded and do not advance the clock while a log is
- * open.  A dat_closed_loop call that would pass hl_capacity returns an error before it launches anything:
- * states, warm state and log are untouched (dat_log_read_*, dat_log_clear, then call again).
+ * dat_control_steps, dat_rollout, dat_rp_rollout, dat_pmrl_rollout and dat_pmrl_forward are NOT recorded and do not
+ * advance the clock while a log is open.  A dat_closed_loop call that would pass hl_capacity returns an error before
+ * it launches anything: states, warm state and log are untouched (dat_log_read_*, dat_log_clear, then call again).
  *
  * Full tier, per slot:
  *   HL record k, after control step k (example/rqp_example.py:121-129): f_des (3n, agent-major), iters (-1 for
