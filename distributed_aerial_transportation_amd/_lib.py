@@ -163,6 +163,8 @@ EXPORTS = {
     "dat_set_sub_batches": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_set_advance_overlap": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_set_step_pipeline": (ctypes.c_int, [H, ctypes.c_int]),
+    "dat_set_fused_advance": (ctypes.c_int, [H, ctypes.c_int]),
+    "dat_get_fused_launches": (ctypes.c_int, [H, LL, LL]),
     "dat_get_stream_count": (ctypes.c_int, [H]),
     "dat_get_advance_counts": (ctypes.c_int, [H, LL, LL]),
     "dat_debug_advance_split": (ctypes.c_int, [H, U8]),

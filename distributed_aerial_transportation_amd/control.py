@@ -382,6 +382,16 @@ class BatchedController:
         """dat_set_step_pipeline: the next step's drain of the advanced scenarios starts beside the ramp-down."""
         L.check(self._lib.dat_set_step_pipeline(self._h, int(bool(on))))
 
+    def set_fused_advance(self, on: bool) -> None:
+        """dat_set_fused_advance: a pass's rollout, desired acceleration and env rows in one launch (k_advance)."""
+        L.check(self._lib.dat_set_fused_advance(self._h, int(bool(on))))
+
+    def fused_launches(self) -> Tuple[int, int]:
+        """dat_get_fused_launches: launches of (k_advance, k_bucket_scatter) since the handle was made."""
+        a, s = ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(self._lib.dat_get_fused_launches(self._h, ctypes.byref(a), ctypes.byref(s)))
+        return a.value, s.value
+
     def stream_count(self) -> int:
         """dat_get_stream_count: streams the handle holds at the moment."""
         m = self._lib.dat_get_stream_count(self._h)

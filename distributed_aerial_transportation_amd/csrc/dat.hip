@@ -305,24 +305,16 @@ __device__ EnvOut env_rows_coop(const double* prm, int n, const double* st, cons
   return out;
 }
 
-// Two wavefronts per SIMD (256 VGPRs, 104 B/lane of scratch for the sorted row slots): the build without
-// the bound (290 registers, no scratch, one wavefront per SIMD) measured slower, C4 A/B 3.58 / 3.61 ->
-// 3.70 / 3.80 ms per step (round 4).  Three or four wavefronts per SIMD (168 / 128 VGPRs, the sorted row
-// slots spilled) measured 3.2-3.6x slower by kernel trace: 0.24 -> 0.77 / 0.87 ms (round 4).
-// ADV (dat_kargs.hpp): the scenarios that take part; a scenario's lanes do together or not at all, the others are
-// carried through the barriers like the lanes past the batch.  ADV_ALL compiles to the kernel without a gate.
+// The body of k_env_class for the lanes of one block (lane ls * n + i: agent i of scenario sc; valid: the scenario
+// takes part), stated once for k_env_class and k_advance.  Every lane of the block must call it (barriers inside).
+// nd, cl, md: 64 words of LDS each; ent: 64 x ENV_CS doubles.  lhs, rhs: the lane's sorted row slots, the
+// kernel's own arrays: declared here they would be optimised once with this function and again with the kernel
+// it is inlined into, and come out wholly scalarised, past the register bound (k_env_class: 180 B/lane of scratch
+// against 88 before the body was factored out; as the kernel's, none at 230 VGPRs).
 template <int ADV>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_env_class(KArgs a) {
-  __shared__ int nd[64], cl[64];
-  __shared__ double md[64];
-  __shared__ double ent[64 * ENV_CS];
-  const int n = a.n, G = 64 / n, NT = G * n;
-  const int lane = threadIdx.x;
-  const int ls = lane / n, i = lane - ls * n;
-  const int sc = blockIdx.x * G + ls;
-  const bool valid = (lane < NT) && (sc < a.B) && adv_gate<ADV, false>(a, sc);
-  if constexpr (ADV != ADV_ALL)
-    if (!__syncthreads_or(valid)) return;  // no scenario of the block takes part
+__device__ __forceinline__ void env_class_lanes(const KArgs& a, int n, int lane, int ls, int i, int sc, bool valid,
+                                                int* nd, int* cl, double* md, double* ent, double lhs[DAT_NENV][3],
+                                                double rhs[DAT_NENV]) {
   int need = 0, col = 0;
   double dist = 1e300;
   const double* prm = valid ? prm_of(a, sc) : a.params;
@@ -330,7 +322,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
   int nt = 0;
   if (valid) forest_of(a, sc, &trees, &nt);
   unsigned emask;
-  double lhs[DAT_NENV][3], rhs[DAT_NENV];
   EnvOut e = env_rows_coop(prm, n, valid ? a.state + (size_t)sc * a.S : nullptr, trees, nt, i, ls, valid,
                            prm[DAT_P_AENVD], &emask, lhs, rhs, ent);
   if (valid) {
@@ -393,6 +384,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
     if (cmin == cmin && key < *(volatile unsigned long long*)pm) atomicMin(pm, key);
   }
 }
+// Two wavefronts per SIMD (256 VGPRs at most): the build without the bound (290 registers, no scratch, one wavefront
+// per SIMD) measured slower, C4 A/B 3.58 / 3.61 -> 3.70 / 3.80 ms per step (round 4).  Three or four wavefronts
+// per SIMD (168 / 128 VGPRs, the sorted row slots spilled) measured 3.2-3.6x slower by kernel trace: 0.24 ->
+// 0.77 / 0.87 ms (round 4).
+// ADV (dat_kargs.hpp): the scenarios that take part; a scenario's lanes do together or not at all, the others are
+// carried through the barriers like the lanes past the batch.  ADV_ALL compiles to the kernel without a gate.
+template <int ADV>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_env_class(KArgs a) {
+  __shared__ int nd[64], cl[64];
+  __shared__ double md[64];
+  __shared__ double ent[64 * ENV_CS];
+  const int n = a.n, G = 64 / n, NT = G * n;
+  const int lane = threadIdx.x;
+  const int ls = lane / n, i = lane - ls * n;
+  const int sc = blockIdx.x * G + ls;
+  const bool valid = (lane < NT) && (sc < a.B) && adv_gate<ADV, false>(a, sc);
+  if constexpr (ADV != ADV_ALL)
+    if (!__syncthreads_or(valid)) return;  // no scenario of the block takes part
+  double lhs[DAT_NENV][3], rhs[DAT_NENV];
+  env_class_lanes<ADV>(a, n, lane, ls, i, sc, valid, nd, cl, md, ent, lhs, rhs);
+}
 
 // Counting sort of the scenario ids by key (need[] in [0, NKEY)): list holds the ids of key 0, then
 // key 1, ...; count is the class table (ScountRow, dat_kargs.hpp): size / start of env class c (keys c NIB ..
@@ -410,19 +422,42 @@ static_assert(NKEY_ALL <= BUCKET_T, "bucket_sort initialises one key per thread"
 // two drains share a stream, and two of them holding stalled scenarios run one after the other.  need[] of a
 // scenario the early pass left out may be stale (its env rows are not computed yet) and is not read by the ADV_EARLY
 // sort.  ADV_ALL: every scenario (adv is not read).
+// Does the sort of mode ADV list scenario q?
+template <int ADV>
+__device__ __forceinline__ bool sort_takes(int q, const int* need, const int* adv, int serial) {
+  if constexpr (ADV == ADV_ALL) return true;
+  else return (adv[q] == serial && need[q] < NKEY) == (ADV == ADV_EARLY);
+}
+// The class table of a sorted list from its keys' sizes and starts (one thread)
+__device__ __forceinline__ void class_table(int* count, const int* tot, const int* kstart) {
+  int st = 0;
+  for (int cl = 0; cl < NCLS; ++cl) {
+    int sz = 0;
+    for (int b = 0; b < NIB; ++b) sz += tot[cl * NIB + b];
+    count[sc_at(SC_SIZE, cl)] = sz;
+    count[sc_at(SC_START, cl)] = st;
+    count[sc_at(SC_HEAD, cl)] = 0;       // queue head of the class (k_cadmm)
+    count[sc_at(SC_HAND_SIZE, cl)] = 0;  // hand-over list of the class (k_cadmm -> k_cadmm_tail) and its head
+    count[sc_at(SC_HAND_HEAD, cl)] = 0;
+    st += sz;
+  }
+  for (int cl = 0; cl < NCLS; ++cl) {  // the tail-routed stretches (keys NKEY + class) behind them
+    count[sc_at(SC_TAIL_SIZE, cl)] = tot[NKEY + cl];
+    count[sc_at(SC_TAIL_START, cl)] = kstart[NKEY + cl];
+    count[sc_at(SC_TAIL_HEAD, cl)] = 0;
+  }
+}
+__device__ __forceinline__ int sort_key(int need) { return min(max(need, 0), NKEY_ALL - 1); }
 template <int ADV>
 __device__ __forceinline__ void bucket_sort(int B, const int* need, int* list, int* count, const int* adv,
                                             int serial) {
-  const auto take = [&](int q) {
-    if constexpr (ADV == ADV_ALL) return true;
-    else return (adv[q] == serial && need[q] < NKEY) == (ADV == ADV_EARLY);
-  };
+  const auto take = [&](int q) { return sort_takes<ADV>(q, need, adv, serial); };
   __shared__ int hist[NKEY_ALL], kstart[NKEY_ALL], cursor[NKEY_ALL], tot[NKEY_ALL];
   const int t = threadIdx.x;
   if (t < NKEY_ALL) { hist[t] = 0; cursor[t] = 0; }
   __syncthreads();
   for (int q = t; q < B; q += BUCKET_T)
-    if (take(q)) atomicAdd(&hist[min(max(need[q], 0), NKEY_ALL - 1)], 1);
+    if (take(q)) atomicAdd(&hist[sort_key(need[q])], 1);
   __syncthreads();
   if (t == 0) {
     int st = 0;
@@ -431,27 +466,10 @@ __device__ __forceinline__ void bucket_sort(int B, const int* need, int* list, i
   __syncthreads();
   for (int q = t; q < B; q += BUCKET_T) {
     if (!take(q)) continue;
-    const int key = min(max(need[q], 0), NKEY_ALL - 1);
+    const int key = sort_key(need[q]);
     list[kstart[key] + atomicAdd(&cursor[key], 1)] = q;
   }
-  if (t == 0) {
-    int st = 0;
-    for (int cl = 0; cl < NCLS; ++cl) {
-      int sz = 0;
-      for (int b = 0; b < NIB; ++b) sz += tot[cl * NIB + b];
-      count[sc_at(SC_SIZE, cl)] = sz;
-      count[sc_at(SC_START, cl)] = st;
-      count[sc_at(SC_HEAD, cl)] = 0;       // queue head of the class (k_cadmm)
-      count[sc_at(SC_HAND_SIZE, cl)] = 0;  // hand-over list of the class (k_cadmm -> k_cadmm_tail) and its head
-      count[sc_at(SC_HAND_HEAD, cl)] = 0;
-      st += sz;
-    }
-    for (int cl = 0; cl < NCLS; ++cl) {  // the tail-routed stretches (keys NKEY + class) behind them
-      count[sc_at(SC_TAIL_SIZE, cl)] = tot[NKEY + cl];
-      count[sc_at(SC_TAIL_START, cl)] = kstart[NKEY + cl];
-      count[sc_at(SC_TAIL_HEAD, cl)] = 0;
-    }
-  }
+  if (t == 0) class_table(count, tot, kstart);
 }
 __global__ __launch_bounds__(BUCKET_T) void k_bucket(int B, const int* need, int* list, int* count) {
   bucket_sort<ADV_ALL>(B, need, list, count, nullptr, 0);
@@ -461,6 +479,64 @@ __global__ __launch_bounds__(BUCKET_T) void k_bucket_adv(int B, const int* need,
                                                          const int* adv, int serial) {
   static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the unfiltered sort is k_bucket");
   bucket_sort<ADV>(B, need, list, count, adv, serial);
+}
+
+// The filtered sort behind k_advance, which has counted the keys where it made them: a key table (KeyTab) holds the
+// histogram of exactly the scenarios sort_takes<ADV> lists -- the early k_advance counts a scenario with a key below
+// NKEY into the main drain's table and a tail-routed one into the rest drain's, the late one everything into the
+// rest drain's -- so the sort is the scatter alone, over SCATTER_T scenarios per block.  Every block derives the key
+// starts from the counts (first wavefront, three keys per lane); a block ranks its scenarios within their keys in
+// LDS and claims a stretch per key it holds with one cursor atomic (the order within a key is not fixed, as in
+// bucket_sort); block 0 writes the class table.  (A claim per wavefront and key, one after the other, left the
+// 65,536-scenario sort at the single workgroup's 66 us: 1,024 wavefronts' claims queue on the few keys most
+// scenarios share.)
+// The tables alternate (two per drain kind): the last block zeroes `other`, the table of the same kind whose
+// previous reader ended before this kernel started and whose next k_advance starts after it has ended
+// (closed_loop_pipelined), so no launch waits for a zeroed table.
+constexpr int SCATTER_T = 256;
+constexpr int KT_COUNT = 0, KT_CURSOR = NKEY_ALL, KT_INTS = 2 * NKEY_ALL;  // KeyTab: counts, then scatter cursors
+static_assert(NKEY_ALL <= 3 * 64, "k_bucket_scatter scans three keys per lane of one wavefront");
+static_assert(NKEY_ALL <= SCATTER_T, "k_bucket_scatter claims one key per thread");
+template <int ADV>
+__global__ __launch_bounds__(SCATTER_T) void k_bucket_scatter(int B, const int* need, int* list, int* count,
+                                                              const int* adv, int serial, int* tab, int* other) {
+  static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the unfiltered sort is k_bucket");
+  __shared__ int kstart[NKEY_ALL], tot[NKEY_ALL], hist[NKEY_ALL], base[NKEY_ALL];
+  const int t = threadIdx.x;
+  if (t < NKEY_ALL) hist[t] = 0;
+  if (t < 64) {  // exclusive prefix sum of the counts
+    int c[3], s = 0;
+    for (int j = 0; j < 3; ++j) {
+      const int k = 3 * t + j;
+      c[j] = k < NKEY_ALL ? tab[KT_COUNT + k] : 0;
+      s += c[j];
+    }
+    int incl = s;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int v = __shfl_up(incl, off);
+      if (t >= off) incl += v;
+    }
+    int st = incl - s;
+    for (int j = 0; j < 3; ++j) {
+      const int k = 3 * t + j;
+      if (k < NKEY_ALL) { kstart[k] = st; tot[k] = c[j]; }
+      st += c[j];
+    }
+  }
+  __syncthreads();
+  const int q = blockIdx.x * SCATTER_T + t;
+  const bool take = q < B && sort_takes<ADV>(q, need, adv, serial);
+  const int key = take ? sort_key(need[q]) : -1;
+  // the block's rank within its key (LDS), then one claim per key the block holds, all keys' claims in flight together
+  const int rank = take ? atomicAdd(&hist[key], 1) : 0;
+  __syncthreads();
+  if (t < NKEY_ALL && hist[t]) base[t] = atomicAdd(tab + KT_CURSOR + t, hist[t]);
+  __syncthreads();
+  const int pos = take ? kstart[key] + base[key] + rank : -1;
+  if ((unsigned)pos < (unsigned)B) list[pos] = q;  // (within the list whatever the tables hold)
+  if (blockIdx.x == 0 && t == 0) class_table(count, tot, kstart);
+  if (blockIdx.x == gridDim.x - 1)
+    for (int k = t; k < KT_INTS; k += SCATTER_T) other[k] = 0;
 }
 
 // Work counters of one wavefront, flushed once per class it drained.
@@ -1382,11 +1458,14 @@ __device__ inline void mountain_of(const KArgs& a, int sc, double* m) {
 // ADV (dat_kargs.hpp): the scenarios that take part.  The early pass runs beside the drain on the scenarios whose
 // done stamp is this step's and reads their f_des as the drain published it (write-through, past the caches); it
 // marks them in adv, and both passes count their scenarios (advcnt).  ADV_ALL compiles to the kernel without a gate.
+// The body of k_rollout_agents for the lanes of one block, stated once for k_rollout_agents and k_advance: the gate
+// and its count, the steps, the write-back and the adv[] mark.  xs: 64 x RO_X doubles of LDS.  Returns false when no
+// scenario of the block takes part (nothing was done: the kernel returns); *took_part: this lane's scenario took part.
 template <bool LOG, int ADV>
-__global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, double dt, const double* fdes,
-                                                       std::conditional_t<LOG, LogArgs, NoLog> lg) {
+__device__ __forceinline__ bool rollout_lanes(const KArgs& a, int steps, double dt, const double* fdes,
+                                              const std::conditional_t<LOG, LogArgs, NoLog>& lg, double* xs,
+                                              bool* took_part) {
   static_assert(!LOG || ADV == ADV_ALL, "the logging rollout is not gated");
-  __shared__ double xs[64 * RO_X];
   const int n = a.n, G = 64 / n, NT = G * n;
   const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
   const int sc = blockIdx.x * G + ls;
@@ -1397,7 +1476,7 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
     // (the stamp is read before the bytes it covers: the loads below are issued after this branch)
     asm volatile("" ::: "memory");
     const unsigned long long took = __ballot(valid && i == 0);
-    if (!took) return;  // no scenario of the block takes part (one wavefront: uniform)
+    if (!took) return false;  // no scenario of the block takes part (one wavefront: uniform)
     if (lane == 0) atomicAdd(a.advcnt + (ADV == ADV_EARLY ? 0 : 1), (unsigned long long)__builtin_popcountll(took));
   }
   const double* prm = valid ? prm_of(a, sc) : a.params;
@@ -1532,6 +1611,15 @@ __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, doubl
       if constexpr (ADV == ADV_EARLY) a.adv[sc] = a.serial;
     }
   }
+  *took_part = valid;
+  return true;
+}
+template <bool LOG, int ADV>
+__global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, double dt, const double* fdes,
+                                                       std::conditional_t<LOG, LogArgs, NoLog> lg) {
+  __shared__ double xs[64 * RO_X];
+  bool took;
+  (void)rollout_lanes<LOG, ADV>(a, steps, dt, fdes, lg, xs, &took);
 }
 
 // lg: the open log's arguments at this launch (dat_closed_loop), or null: the plain kernel
@@ -1705,15 +1793,59 @@ __global__ __launch_bounds__(64) void k_pmrl_forward(KArgs a, const double* f, d
   }
 }
 
-template <int ADV>
-__global__ void k_desired(KArgs a, double* acc) {
-  const int sc = blockIdx.x * blockDim.x + threadIdx.x;
-  if (sc >= a.B || !adv_gate<ADV, false>(a, sc)) return;
+// the desired acceleration of scenario sc from its state in memory (k_desired, k_advance)
+__device__ __forceinline__ void desired_of(const KArgs& a, int sc, double* acc) {
   const double* st = a.state + (size_t)sc * a.S;
   double* o = acc + (size_t)sc * 6;
   double m[DAT_MOUNTAIN_SIZE];
   mountain_of(a, sc, m);
   desired_accel_forest(st, a.n, m, REF_X_OFFSET, o);
+}
+template <int ADV>
+__global__ void k_desired(KArgs a, double* acc) {
+  const int sc = blockIdx.x * blockDim.x + threadIdx.x;
+  if (sc >= a.B || !adv_gate<ADV, false>(a, sc)) return;
+  desired_of(a, sc, acc);
+}
+
+// The advance pass of the closed loop in one launch (dat_set_fused_advance): k_rollout_agents<false, ADV>, k_desired<ADV>
+// and k_env_class<ADV> of a block's G scenarios, through the same device functions on the same inputs, so a
+// scenario's state, acc, env rows and key are bit for bit those of the three launches.  The three share the mapping
+// (lane ls * n + i: agent i) and the gate: the scenarios the rollout takes are the ones it marks (ADV_EARLY) or
+// finds unmarked (ADV_REST), which is the gate of the other two.  The block barrier orders the state's write-back
+// before its reads: k_desired's by the scenario's first lane, the env rows' by every lane, from memory as in the
+// separate kernels.  One grid waits once for the SIMDs the drain's wavefronts free, and the state is not fetched
+// from memory again.  Registers: bound as k_env_class (256); the rollout's are dead at the barrier.
+template <int ADV>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_advance(KArgs a, int steps, double dt,
+                                                                                        const double* fdes,
+                                                                                        double* acc, int* kc_lo,
+                                                                                        int* kc_hi) {
+  static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the ungated step runs the three kernels");
+  __shared__ double xs[64 * RO_X];
+  __shared__ int nd[64], cl[64];
+  __shared__ double md[64];
+  __shared__ double ent[64 * ENV_CS];
+  const int n = a.n, G = 64 / n;
+  const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
+  const int sc = blockIdx.x * G + ls;
+  bool valid;
+  if (!rollout_lanes<false, ADV>(a, steps, dt, fdes, NoLog{}, xs, &valid)) return;
+  __syncthreads();  // the state is stored before it is read back
+  if (valid && i == 0) desired_of(a, sc, acc);
+  double lhs[DAT_NENV][3], rhs[DAT_NENV];
+  env_class_lanes<ADV>(a, n, lane, ls, i, sc, valid, nd, cl, md, ent, lhs, rhs);
+  // the sort's count (k_bucket_scatter), where the keys are made: the block's histogram, then one atomic per key it
+  // holds into the key table of the list the scenario goes to (kc_lo: keys below NKEY, kc_hi: the tail-routed ones;
+  // null: the sort counts for itself)
+  if (kc_lo == nullptr) return;
+  __shared__ int hist[NKEY_ALL];
+  for (int k = lane; k < NKEY_ALL; k += 64) hist[k] = 0;
+  __syncthreads();
+  if (valid && i == 0) atomicAdd(&hist[sort_key(a.need[sc])], 1);  // (the key this lane has just stored)
+  __syncthreads();
+  for (int k = lane; k < NKEY_ALL; k += 64)
+    if (const int c = hist[k]) atomicAdd((k < NKEY ? kc_lo : kc_hi) + KT_COUNT + k, c);
 }
 
 __global__ void k_warm(KArgs a) {
@@ -1971,6 +2103,12 @@ constexpr int DAT_MAX_SUB = 4;  // sub-batches of the C-ADMM closed loop (dat_se
 #ifndef DAT_STEP_PIPELINE_DEFAULT  // (A/B builds, tools/build_var.sh: -DDAT_STEP_PIPELINE_DEFAULT=false / true)
 #define DAT_STEP_PIPELINE_DEFAULT true
 #endif
+#ifndef DAT_FUSED_ADVANCE_DEFAULT  // (likewise: -DDAT_FUSED_ADVANCE_DEFAULT=false / true)
+#define DAT_FUSED_ADVANCE_DEFAULT true
+#endif
+#ifndef DAT_FUSED_SORT  // (A/B builds: 0 keeps k_bucket_adv behind k_advance)
+#define DAT_FUSED_SORT 1
+#endif
 // The closed loop's log (dat_log_begin .. dat_log_end): device buffers filled by k_rollout_agents<true>, the log
 // clock and what dat_log_clear has dropped.  Held records: HL clock / hl_every - hl_base, step
 // ceil(clock / log_every) - step_base.
@@ -2062,6 +2200,11 @@ struct dat_handle {
   // (on the handle's stream): after the rest chain's sort, after the rest drain.
   bool pipe_on = DAT_STEP_PIPELINE_DEFAULT;
   side_stream pipe;
+  // the overlap's and the pipeline's passes (early, rest) as one launch each, k_advance, where a pass runs the
+  // rollout and the next step's inputs (dat_set_fused_advance); off: the three kernels, same results
+  bool fused_on = DAT_FUSED_ADVANCE_DEFAULT;
+  mutable long long n_advance = 0, n_scatter = 0;  // launches of k_advance / k_bucket_scatter (dat_get_fused_launches)
+  int* ktabs = nullptr;  // ... with the pipeline: the key tables of its sorts (4 x KT_INTS: main 0 / 1, rest 0 / 1)
   int* pipe_lists = nullptr;  // slist and rlist of the two pipeline streams' drains (4 x B; the handle's stream: slist, rlist)
   double agent_qp_ms = 0.0;  // device time of the last dat_solve_agent_qp_batch launch
   int ll_kind = 0;  // LL_PD (example/rqp_example.py:113) or LL_SM
@@ -2382,6 +2525,9 @@ struct Sub {
   KArgs a;
   int off;
   hipEvent_t ek, e1;
+  // the step pipeline with the fused advance: the key tables (KeyTab) a pass's k_advance counts into (keys below
+  // NKEY, tail-routed keys), the one a filtered sort reads and the one it zeroes; null: k_bucket_adv counts itself
+  int *kc_lo = nullptr, *kc_hi = nullptr, *ktab = nullptr, *kzero = nullptr;
 };
 Sub sub_batch(const dat_handle* h, int s = 0, int S = 1) {
   const SubRange r = sub_range(h->cfg.batch, s, S);
@@ -2446,7 +2592,12 @@ int launch_control(const dat_handle* h, const Sub& u, int mode = ADV_ALL, int st
   if (h->cfg.mode == DAT_MODE_CADMM) {  // the class sort of the step's keys (k_env_class), the drain
     if (mode == ADV_ALL)
       hipLaunchKernelGGL(k_bucket, dim3(1), dim3(BUCKET_T), 0, u.st, a.B, (const int*)a.need, a.slist, a.scount);
-    else
+    else if (u.ktab) {
+      hipLaunchKernelGGL(mode == ADV_EARLY ? k_bucket_scatter<ADV_EARLY> : k_bucket_scatter<ADV_REST>,
+                         dim3((a.B + SCATTER_T - 1) / SCATTER_T), dim3(SCATTER_T), 0, u.st, a.B, (const int*)a.need,
+                         a.slist, a.scount, (const int*)a.adv, stamp, u.ktab, u.kzero);
+      ++h->n_scatter;
+    } else
       hipLaunchKernelGGL(mode == ADV_EARLY ? k_bucket_adv<ADV_EARLY> : k_bucket_adv<ADV_REST>, dim3(1),
                          dim3(BUCKET_T), 0, u.st, a.B, (const int*)a.need, a.slist, a.scount, (const int*)a.adv, stamp);
     HIPCHK(hipEventRecord(u.ek, u.st));
@@ -2474,6 +2625,28 @@ void launch_step_rollout(const dat_handle* h, const Sub& u, int mode = ADV_ALL) 
   const LogArgs lg = h->log.open ? log_args(h, u.off) : LogArgs();
   launch_rollout(u.a, u.a.B, u.st, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes, h->log.open ? &lg : nullptr,
                  mode);
+}
+
+// A pass (ADV_EARLY / ADV_REST) of the overlap and the pipeline: the rollout of the step and, with `inputs`, the next
+// step's inputs of the scenarios it advanced.  One launch of k_advance where the switch is on (these schedules run
+// C-ADMM on one sub-batch with no log open: advance_ready), else the three kernels of the step chain.
+// fused_ready is the one statement of where k_advance runs: the passes go by it here, and the pipeline hands out key
+// tables (Sub::kc_lo / ktab) by it, so a sort reads a key table only behind passes that counted into it.  A pass
+// that is given a table and would not count (the three kernels do not) is an error, not a silently empty list.
+bool fused_ready(const dat_handle* h) { return h->fused_on && h->cfg.mode == DAT_MODE_CADMM && !h->log.open; }
+int launch_advance(const dat_handle* h, const Sub& u, int mode, bool inputs) {
+  if (inputs && mode != ADV_ALL && fused_ready(h)) {
+    const int G = 64 / u.a.n;
+    hipLaunchKernelGGL(mode == ADV_EARLY ? k_advance<ADV_EARLY> : k_advance<ADV_REST>, dim3((u.a.B + G - 1) / G),
+                       dim3(64), 0, u.st, u.a, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes, (double*)u.a.acc,
+                       u.kc_lo, u.kc_hi);
+    ++h->n_advance;
+    return 0;
+  }
+  if (inputs && u.kc_lo) return fail("launch_advance: a key table was handed to a pass that runs the three kernels");
+  launch_step_rollout(h, u, mode);
+  if (inputs) launch_inputs(h, u, mode);
+  return 0;
 }
 
 double now_ms() {
@@ -2559,6 +2732,10 @@ bool pipeline_ready(dat_handle* h) {
     (void)hipGetLastError();
     return false;
   }
+  if (!h->ktabs && dalloc(h, &h->ktabs, (size_t)4 * KT_INTS)) {
+    (void)hipGetLastError();
+    return false;
+  }
   return true;
 }
 
@@ -2584,6 +2761,14 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
   }
   Sub base = sub_batch(h);
   adv_args(h, base.a);
+  // With the fused advance the passes count the keys of the sorts behind them (k_bucket_scatter).  The key tables of
+  // the passes of step k: the main drain's `main(k)`, the rest drain's `rest(k)`, alternating with the step, each
+  // zeroed by the sort of its kind one step earlier and all of them here, at the call's start (a call ends with the
+  // last counting passes' tables sorted but not zeroed).
+  const bool fsort = fused_ready(h) && DAT_FUSED_SORT;
+  const auto main_tab = [&](int k) { return fsort ? h->ktabs + KT_INTS * (k & 1) : nullptr; };
+  const auto rest_tab = [&](int k) { return fsort ? h->ktabs + KT_INTS * (2 + (k & 1)) : nullptr; };
+  if (fsort) HIPCHK(hipMemsetAsync(h->ktabs, 0, sizeof(int) * 4 * KT_INTS, h->stream));
   // the main drain of step k: on the handle's stream over every scenario (k = 0, the first of the call), else on
   // the stream of the early pass it follows
   const auto main_drain = [&](int k, int serial) {
@@ -2594,6 +2779,8 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
       m.a.slist = h->pipe_lists + (size_t)2 * j * B;
       m.a.rlist = m.a.slist + B;
       m.a.scount = h->scount + SCOUNT_INTS * (1 + j);  // (one sub-batch: the other sub-batches' tables are free)
+      m.ktab = main_tab(k - 1);
+      m.kzero = main_tab(k);
     }
     m.a.serial = serial;
     m.ek = h->sub_ev[2 * (size_t)k];
@@ -2634,10 +2821,11 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
     Sub early = base;
     early.st = x.st;
     early.a.serial = serial;
+    early.kc_lo = main_tab(k);
+    early.kc_hi = rest_tab(k);
     if (k > 0) HIPCHK(hipStreamWaitEvent(x.st, h->pipe.ev[1], 0));
     if (k > 0 && h->advmask) HIPCHK(hipStreamWaitEvent(x.st, h->pipe.ev[2], 0));
-    launch_step_rollout(h, early, ADV_EARLY);
-    if (more) launch_inputs(h, early, ADV_EARLY);
+    if (launch_advance(h, early, ADV_EARLY, more)) return -1;
     HIPCHK(hipEventRecord(x.ev[0], x.st));
     const int next = more ? next_serial(h) : 0;
     if (more && launch_control(h, main_drain(k + 1, next), ADV_EARLY, serial)) return -1;
@@ -2646,11 +2834,12 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
     // word out of it: its queue-empty store goes to a spare word of the class tables.
     Sub rest = base;
     rest.a.serial = serial;
+    rest.kc_lo = rest.kc_hi = rest.ktab = rest_tab(k);
+    rest.kzero = rest_tab(k + 1);
     if (k > 0) HIPCHK(hipStreamWaitEvent(rest.st, e1, 0));
     HIPCHK(hipStreamWaitEvent(rest.st, x.ev[0], 0));
-    launch_step_rollout(h, rest, ADV_REST);
+    if (launch_advance(h, rest, ADV_REST, more)) return -1;
     if (more) {
-      launch_inputs(h, rest, ADV_REST);
       rest.a.serial = next;
       rest.a.qempty = h->scount + SCOUNT_INTS * 3;
       rest.ek = h->pipe.ev[1];
@@ -3260,13 +3449,11 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
         // the passes after the drain: the rollout, then (not after the call's last step) the next step's inputs
         Sub early = v;
         early.st = h->advance.st;
-        launch_step_rollout(h, early, ADV_EARLY);
-        if (k + 1 < hl_steps) launch_inputs(h, early, ADV_EARLY);
+        if (launch_advance(h, early, ADV_EARLY, k + 1 < hl_steps)) return -1;
         HIPCHK(hipEventRecord(h->advance.ev[0], early.st));
         // (the rest pass is enqueued before the wait for the drain, so that its end finds it in the queue)
         HIPCHK(hipStreamWaitEvent(v.st, h->advance.ev[0], 0));
-        launch_step_rollout(h, v, ADV_REST);
-        if (k + 1 < hl_steps) launch_inputs(h, v, ADV_REST);
+        if (launch_advance(h, v, ADV_REST, k + 1 < hl_steps)) return -1;
       }
       HIPCHK(hipGetLastError());
     }
@@ -3384,6 +3571,19 @@ int dat_set_advance_overlap(dat_handle* h, int on) {
 int dat_set_step_pipeline(dat_handle* h, int on) {
   if (!h) return fail("null handle");
   h->pipe_on = on != 0;
+  return 0;
+}
+
+int dat_set_fused_advance(dat_handle* h, int on) {
+  if (!h) return fail("null handle");
+  h->fused_on = on != 0;
+  return 0;
+}
+
+int dat_get_fused_launches(dat_handle* h, long long* advance, long long* scatter) {
+  if (!h) return fail("null handle");
+  if (advance) *advance = h->n_advance;
+  if (scatter) *scatter = h->n_scatter;
   return 0;
 }
 

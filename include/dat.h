@@ -219,6 +219,19 @@ int dat_set_advance_overlap(dat_handle* h, int on);
  * spans, which overlap between consecutive steps; the step marks are taken when the host first finds a step's main
  * drain ended. */
 int dat_set_step_pipeline(dat_handle* h, int on);
+/* Where the advance overlap or the step pipeline runs: the fused advance (default on).  A pass (early or late) that
+ * runs the rollout and the next step's inputs of its scenarios does so in one launch, k_advance, instead of three
+ * (rollout, desired acceleration, env rows and keys): one grid, the state written once and read back by the block
+ * that wrote it.  The launch calls the device functions the three kernels call, on the same inputs in the same
+ * order, so every result is bitwise that of on = 0, which runs the three kernels.  Under the step pipeline the
+ * launch also counts the sort keys it makes, and the sorts of the two drains behind it only scatter, on many
+ * workgroups (which scenarios share a wavefront is fixed by neither sort).  The passes that run only a part
+ * -- a call's first step (inputs up front) and last step (rollouts only) -- and every schedule that does not split
+ * the advance (serial, sub-batches, a log, the other modes, the step-by-step entry points) keep the three kernels. */
+int dat_set_fused_advance(dat_handle* h, int on);
+/* Launches of k_advance and of k_bucket_scatter (the sort behind it under the step pipeline) since the handle was
+ * made: what tells the fused advance from its fall-backs, whose results are the same by construction. */
+int dat_get_fused_launches(dat_handle* h, long long* advance, long long* scatter);
 /* Streams the handle holds at the moment (its own, and the side streams made on first use): never more than four.
  * dat_set_sub_batches gives back the streams its new count does not use. */
 int dat_get_stream_count(dat_handle* h);
