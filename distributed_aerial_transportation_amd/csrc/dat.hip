@@ -1204,7 +1204,7 @@ constexpr int DD_SLOT_INTS = 64;  // ints of each per-slot array of k_dd (G <= 2
 struct DdLds {
   double *X, *lamF, *lamM, *E, *Rts, *red, *envs;
   QPShared* shs;
-  int *sid, *done, *wmx, *end;
+  int *sid, *done, *wmx, *lng, *end;
   size_t bytes() const { return (size_t)((char*)end - (char*)X); }
 };
 __host__ __device__ inline DdLds dd_carve(double* smem, int n, bool env) {
@@ -1221,7 +1221,8 @@ __host__ __device__ inline DdLds dd_carve(double* smem, int n, bool env) {
   L.sid = (int*)(L.envs + dd_area_doubles(env));    // G: scenario of the slot (-1 empty, -2 retired)
   L.done = L.sid + DD_SLOT_INTS;                    // G: the slot's scenario stopped in this pass
   L.wmx = L.done + DD_SLOT_INTS;                    // G: IPM iterations of the slot's slowest agent QP this step
-  L.end = L.wmx + DD_SLOT_INTS;
+  L.lng = L.wmx + DD_SLOT_INTS;                     // G: the slot's chain is a long one (dd_long_chain)
+  L.end = L.lng + DD_SLOT_INTS;
   return L;
 }
 // k_dd_key: drain-order key of every scenario -- the previous step's (DD iteration count, slowest agent
@@ -1282,6 +1283,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       L.sid[ls] = q < cnt ? a.slist[first + q] : -2;
       L.done[ls] = 0;
       L.wmx[ls] = 0;
+      L.lng[ls] = 0;
     }
     __syncthreads();
     const int slot_sc = lane < NT ? L.sid[ls] : -2;
@@ -1336,15 +1338,18 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       IPMOut o;
       const double* y0 = prm + DAT_P_FEQ(n) + 3 * i;
       DAT_PHASE(10);
-      // a late DD pass: the agent QP differs from the previous pass's only in its prices, so it starts from that
-      // pass's last iterate (ipm_solve WS, the tail kernel's warm start)
-      const bool wson = dd_warm_pass(iter);
+      // a late pass of a long chain: the agent QP differs from the previous pass's only in its prices, so it starts
+      // from that pass's last iterate (ipm_solve WS, the tail kernel's warm start); a long chain's QPs are solved
+      // tighter (dd_qp_tol, dat_dd_step.hpp)
+      const bool lng = L.lng[ls] != 0;
+      const bool wson = dd_warm_start(iter, lng);
+      const double qtol = dd_qp_tol(lng, a.qp_tol);
       if constexpr (ENV)
-        o = ipm_solve_rows<MODE_DD, 1, IPM_FAST, true>(nr, shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER, a.qp_tol,
-                                                       wrl, wson);
+        o = ipm_solve_rows<MODE_DD, 1, IPM_FAST, true>(nr, shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER, qtol, wrl,
+                                                       wson);
       else
         o = ipm_solve<MODE_DD, 1, NBASE, LdsRef<QPShared>, EnvLds, RtLds, RowRegs, 0, NoGrp, IPM_FAST, true>(
-            shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowRegs{}, NoGrp{}, wrl, wson);
+            shr, err, rtr, P, y0, y, w, bst, IPM_MAX_ITER, qtol, RowRegs{}, NoGrp{}, wrl, wson);
       DAT_PHASE(9);
       wc.ipm += o.iters;
       wc.inband += o.inband;
@@ -1378,6 +1383,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
       const bool stop = dd_stop(res, a.res_tol, iter, a.max_iter);
       if (!stop && a.record_err && a.err) a.err[(size_t)sc * (a.max_iter + 1) + iter - 1] = res;
       L.done[ls] = stop ? 1 : 0;
+      if (!stop && dd_long_chain(iter, res)) L.lng[ls] = 1;
     }
     __syncthreads();
     if (active) {
@@ -1415,6 +1421,7 @@ __global__ __launch_bounds__(64) void k_dd(KArgs a) {
             build_shared(S, prm, n, a.state + (size_t)sc * a.S, a.acc + ((size_t)kstep * a.B + sc) * 6,
                          prm[DAT_P_KFD], prm[DAT_P_KMD], 3, false);
             L.wmx[ls] = 0;
+            L.lng[ls] = 0;
           }
         } else if (i == 0) {
           L.sid[ls] = -1;

@@ -20,7 +20,23 @@ namespace dat {
 // every DD parity test green (golden sequences, the DD hard stretch, the 100 s loop to the same horizon).  (The
 // round-5 DD ran every pass cold; the build option that kept it for A/B builds went with this header.)
 constexpr int DD_WARM_PASS = 30;
+// The long-chain rule.  A cold agent-QP solve stops on the central path at a gap of 3-8e-10 (the first iterate under
+// 10 tol), the same point pass after pass: its offset from the minimiser (the QPs are strongly convex only through
+// the 1e-6 regularisation in some directions) is constant and the dual ascent absorbs it.  A warm solve stops
+// elsewhere, so the first warm pass moved the residual by up to 4.5e-4 relative against the oracle's cold 1e-11
+// solves (n = 8, a 44-pass step; the all-cold step 3e-5), beyond the oracle's own sensitivity (tests/_dd_long.py).
+// A chain that is still DD_LONG_RES from consensus after DD_LONG_PASS passes is a long one (ordinary steps stop
+// after ~4): from then on its agent QPs, cold and warm alike, are solved DD_LONG_TOL times tighter, which makes both
+// offsets ten times smaller where the residual is still large, and only such a chain starts warm.  Host step,
+// ref_dd_long.npz: IPM iterations per solve 10.4 -> 10.8 cold, 5.5 -> 5.9 warm.
+constexpr int DD_LONG_PASS = 6;
+constexpr double DD_LONG_RES = 0.5, DD_LONG_TOL = 0.1;
+// after `iter` passes with residual res: the chain is a long one from here on
+DAT_HD bool dd_long_chain(int iter, double res) { return iter == DD_LONG_PASS && res >= DD_LONG_RES; }
+DAT_HD double dd_qp_tol(bool lng, double tol) { return lng ? fmax(DD_LONG_TOL * tol, 1e-12) : tol; }
 DAT_HD bool dd_warm_pass(int iter) { return iter >= DD_WARM_PASS; }
+// the agent QPs of pass `iter` start warm: a warm pass of a long chain
+DAT_HD bool dd_warm_start(int iter, bool lng) { return lng && dd_warm_pass(iter); }
 // The drain-order key's bin of a step's slowest agent QP (k_dd_key).  DD agent QPs run the conservative IPM start
 // (9-10 iterations on average): bins <= 8, 9-10, 11-13, >= 14.
 DAT_HD int dd_ipm_bin(int it) { return it <= 8 ? 0 : it <= 10 ? 1 : it <= 13 ? 2 : 3; }

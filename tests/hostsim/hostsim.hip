@@ -254,6 +254,7 @@ int hs_dd_step(const double* prm, int n, const double* st, const double* acc, co
     nr = nr > rows_needed(P[i].emask) ? nr : rows_needed(P[i].emask);
   }
   int iter = 0;
+  bool lng = false;  // the long-chain rule (dd_long_chain)
   *ipmx = 0;
   for (;;) {
     for (int i = 0; i < n; ++i) {
@@ -262,8 +263,8 @@ int hs_dd_step(const double* prm, int n, const double* st, const double* acc, co
       set_dd_price(P[i], prm, n, i, c9);
       const IPMOut o = ipm_solve_rows<MODE_DD, 1, IPM_FAST, true>(
           nr, PlainRef<QPShared>{&S}, EnvPlain{&Ev[i]}, RtPtr{Rts.data() + 9 * i}, P[i], prm + DAT_P_FEQ(n) + 3 * i, y,
-          w, best.data() + (size_t)i * best_size(1), 50, qp_tol, wrec.data() + (size_t)i * WREC_SIZE,
-          dd_warm_pass(iter));
+          w, best.data() + (size_t)i * best_size(1), 50, dd_qp_tol(lng, qp_tol), wrec.data() + (size_t)i * WREC_SIZE,
+          dd_warm_start(iter, lng));
       diag(o);
       *ipmx = *ipmx > o.iters ? *ipmx : o.iters;
       qstatus[i] = o.status;
@@ -275,6 +276,7 @@ int hs_dd_step(const double* prm, int n, const double* st, const double* acc, co
     const double res = dd_pass_residual(E.data(), 6, n);
     if (dd_stop(res, res_tol, iter, max_iter)) break;
     err_seq[iter - 1] = res;
+    lng = lng || dd_long_chain(iter, res);
     for (int i = 0; i < n; ++i)
       dd_dual_ascent(Hinv + (size_t)(6 * i) * N6, N6, E.data(), 6, n, lamF + 3 * i, lamM + 3 * i);
   }
