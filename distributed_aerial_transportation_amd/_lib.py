@@ -16,21 +16,22 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 LIB_PATH = os.path.join(PKG, "libdat.so")
-SRC = os.path.join(PKG, "csrc", "dat.hip")
-SRC_CENT = os.path.join(PKG, "csrc", "dat_cent.hip")  # k_cent<n>: its own translation unit, compiled in parallel
-SRC_COMM = os.path.join(PKG, "csrc", "dat_comm.hip")  # RCCL metric collectives (dat_comm_*)
-SRCS = (SRC, SRC_CENT, SRC_COMM)
+CSRC = os.path.join(PKG, "csrc")
+# The library's translation units, compiled in parallel: every .hip under csrc/ -- dat.hip (host side: handle, step
+# chain, C-ABI), the kernel units dat_k_*.hip (csrc/dat_launch.hpp lists them), dat_cent.hip (k_cent<n>), dat_comm.hip
+# (RCCL metric collectives) -- but the unity file, which is all of dat.hip's as one unit for development builds
+# (tools/build_var.sh).
+UNITY = os.path.join(CSRC, "dat_unity.hip")
+SRCS = tuple(sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip") and f != os.path.basename(UNITY)))
 OBJ_DIR = os.path.join(PKG, "build")
 # -ffp-contract=on: multiply-adds fused within a source expression only (not across statements, which
 # depends on the inlining context): an inlined function computes the same bits at every call site and in
 # every kernel (k_cadmm / k_cadmm_tail run the same agent-QP passes, dat_qp.hpp).  C4 A/B: k_cadmm 3.53 ->
 # 3.55 ms per step.
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on"]
-DEPS = [SRC, SRC_CENT, SRC_COMM, os.path.join(PKG, "csrc", "dat_core.hpp"), os.path.join(PKG, "csrc", "dat_qp.hpp"),
-        os.path.join(PKG, "csrc", "dat_cadmm_step.hpp"), os.path.join(PKG, "csrc", "dat_dd_step.hpp"),
-        os.path.join(PKG, "csrc", "dat_pmrl_step.hpp"), os.path.join(PKG, "csrc", "dat_kargs.hpp"),
-        os.path.join(PKG, "csrc", "dat_ckpt.hpp"),
-        os.path.join(PKG, "csrc", "dat_layout.h"), os.path.join(REPO, "include", "dat.h")]
+# what the source hash covers: every file under csrc/ (by listing it: a new header cannot be left out) and the C-ABI
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))) + [
+    os.path.join(REPO, "include", "dat.h")]
 
 MODE_CENTRALIZED, MODE_CADMM, MODE_DD = 0, 1, 2
 QP_OPTIMAL, QP_INACCURATE, QP_INFEASIBLE, QP_FAILED = 0, 1, 2, 3

@@ -1,5 +1,5 @@
 // dat_cadmm_step.hpp -- the lane-level rules of the C-ADMM control step (control/rqp_cadmm.py:631-675), each
-// stated once for every build that runs the step: the GPU drain (dat.hip cadmm_drain, k_agent_qp), the CPU
+// stated once for every build that runs the step: the GPU drain (cadmm_drain, dat_cadmm_drain.hpp; k_agent_qp), the CPU
 // baseline (cpu_baseline/dat_cpu.hip) and the test-only host build (tests/hostsim).  A GPU lane calls them for
 // its agent i between the drain's barriers; a host build calls them in a loop over i < n.  Every floating-point
 // expression stands whole inside one function: with -ffp-contract=on (multiply-adds fused within an expression

@@ -1,5 +1,5 @@
 // dat_cent.hip -- the centralized QP kernel (control/rqp_centralized.py:27-455): one lane group per
-// QP, one lane per agent's force.  Its own translation unit (compiled in parallel with dat.hip by
+// QP, one lane per agent's force.  Its own translation unit (compiled in parallel with the other units by
 // distributed_aerial_transportation_amd/_lib.py and linked into libdat.so).
 //
 // The centralized QP couples the n agents' forces only through the aggregate wrench u = sum_k U_k f_k

@@ -521,7 +521,7 @@ DAT_HD double capsule_tree(const double* x0, const double* d, double rc, const d
 }
 
 // The pieces of the env CBF rows (control/rqp_cadmm.py:307-373), each stated once: env_rows runs them tree after
-// tree for one solve, env_rows_coop (dat.hip) one tree per lane for the agents of a scenario.  Every
+// tree for one solve, env_rows_coop (dat_k_step.hip) one tree per lane for the agents of a scenario.  Every
 // floating-point expression stands whole inside one piece (the rule of dat_cadmm_step.hpp), so both compute the
 // same bits.
 constexpr double ENV_TOUCH = 1e-4;  // a tree closer than this is a collision and gives no row

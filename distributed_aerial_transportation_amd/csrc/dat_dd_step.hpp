@@ -1,6 +1,6 @@
 // dat_dd_step.hpp -- the lane-level rules of the dual-decomposition (DD) control step (control/rqp_dd.py:513-555,
-// 642-693, 695-752), each stated once for every build that runs the step: the GPU kernels (dat.hip k_dd_setup,
-// k_dd) and the test-only host build (tests/hostsim).  A GPU lane calls them for its agent i (or its element of a
+// 642-693, 695-752), each stated once for every build that runs the step: the GPU kernels (k_dd_setup, dat_k_dd.hip;
+// k_dd, dat_dd_drain.hpp) and the test-only host build (tests/hostsim).  A GPU lane calls them for its agent i (or its element of a
 // matrix) between the kernels' barriers; a host build calls them in a loop.  Every floating-point expression
 // stands whole inside one function: with -ffp-contract=on (multiply-adds fused within an expression only) an
 // inlined copy computes the same bits at every call site.

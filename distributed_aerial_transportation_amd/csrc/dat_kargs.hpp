@@ -1,5 +1,6 @@
 // dat_kargs.hpp -- kernel arguments and launch-wide constants shared by the translation units of
-// libdat.so (dat.hip: C-ADMM, DD, rollout, C-ABI; dat_cent.hip: the centralized kernel).
+// libdat.so (dat.hip: the host side and the C-ABI; the kernel units dat_k_*.hip, dat_launch.hpp; dat_cent.hip: the
+// centralized kernel).
 #pragma once
 
 #include "dat_cadmm_step.hpp"

@@ -15,7 +15,7 @@
 // down).  And G T = z: the payload's force sum q T = sqrt(ml) z[0:3] and Jl^-1 c T = U' z[3:6] follow from z, no
 // second sum over the links.  
 //
-// The pieces below are what a GPU lane (k_pmrl_rollout / k_pmrl_forward, dat.hip: one lane per link, (m_i, y_i,
+// The pieces below are what a GPU lane (k_pmrl_rollout / k_pmrl_forward, dat_k_step.hip: one lane per link, (m_i, y_i,
 // g_i) through LDS) and the serial host forms at the end of this file (pmrl_forward, pmrl_step: the test builds)
 // both run.  Every floating-point expression stands whole inside one piece (the rule of dat_cadmm_step.hpp); the
 // sums over the links run in the order i = 0 .. n-1 in both.

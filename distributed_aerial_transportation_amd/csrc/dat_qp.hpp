@@ -226,7 +226,7 @@ constexpr int WREC_SIZE = 28 + 2 * DAT_MAXROW;
 // The tail rule of the C-ADMM closed loop with a forest: ADMM pass p of a scenario's control step solves its
 // agent QPs with the warm start and the stall exit exactly when p >= 1 and (the scenario's previous step took more
 // than TAIL_PREV passes -- it is wedged in a stall, where every step is the reference loop's 101-pass max_iter
-// stall, control/rqp_cadmm.py:661 -- or p >= TAIL_PASS).  The GPU runs those passes in k_cadmm_tail (dat.hip).
+// stall, control/rqp_cadmm.py:661 -- or p >= TAIL_PASS).  The GPU runs those passes in k_cadmm_tail (dat_k_cadmm_tail.hip).
 // The rule depends on the scenario's own history only, so its results do not depend on the scenarios it is
 // batched with.  Normal C4 steps take 1-14 passes: the warm closed loop never meets it.
 // (TAIL_PASS = 8 measured worse: the warm window's 9-14-pass scenarios then finish after k_cadmm, C4 3.87 -> 4.58

@@ -58,7 +58,7 @@ def test_gpu_c4_stall_stretches_match_oracle():
 def test_gpu_c4_stall_sub_batches_bitwise():
     """The wedged scenarios' steps do not depend on the schedule: with one sub-batch k_env_class routes them to
     the tail launch beside k_cadmm (KArgs::route), with two k_cadmm hands them over before their first pass
-    (dat.hip cadmm_drain, `wedged`); both runs of the closed loop (the stretches' 2 scenarios twice) end bitwise
+    (dat_cadmm_drain.hpp cadmm_drain, `wedged`); both runs of the closed loop (the stretches' 2 scenarios twice) end bitwise
     equal after 3 HL steps, the last two of them 101-pass stalls."""
     from distributed_aerial_transportation_amd import BatchedController, Forest, scenarios
 

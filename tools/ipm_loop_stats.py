@@ -2,8 +2,12 @@
 """Static instruction statistics of the IPM iteration loops in the emitted gfx950 assembly.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -S --cuda-device-only \
-        distributed_aerial_transportation_amd/csrc/dat.hip -o dat.s
+        distributed_aerial_transportation_amd/csrc/dat_k_cadmm.hip -o dat.s
     python tools/ipm_loop_stats.py dat.s [--kernels k_cadmm,k_cadmm0,k_cadmm_tail,k_dd] [--min-valu 3000]
+
+The IPM kernels live in three units (csrc/dat_launch.hpp): dat_k_cadmm.hip (k_cadmm, k_cadmm0, k_dd, above),
+dat_k_cadmm_adv.hip (their advance-overlap instantiations) and dat_k_cadmm_tail.hip (the tail kernels, k_agent_qp);
+csrc/dat_unity.hip is all of them as one unit, with the same device code.
 
 The compiler annotates every basic block with the loop it belongs to ("=>This Loop Header", "Parent Loop",
 "in Loop: Header=").  An IPM iteration loop (ipm_attempt's `for (it = 0;; ++it)`) is recognised by size: a loop
@@ -174,7 +178,7 @@ def main():
                   f"{c['scr_st']:>7}{c['accvgpr']:>8}{c['lgkm_waits']:>7}{c['lgkm_waits_rd']:>8}{rw:>8.2f}{c['vm_waits']:>6}")
             found += 1
     if not found:
-        print("no IPM loop found (is this the device assembly of dat.hip?)", file=sys.stderr)
+        print("no IPM loop found (is this the device assembly of a unit with IPM kernels?)", file=sys.stderr)
         return 1
     return 0
 

@@ -1,15 +1,19 @@
-"""Is the device code of two builds the same?  Compares two assembly files of a translation unit's device side,
+"""Is the device code of two builds the same?  Compares the assembly of the device side of two builds, each one
+translation unit or several (the kernel units under csrc/, dat_launch.hpp; dat_unity.hip is all of them as one),
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on --cuda-device-only -S dat.hip -o X.s
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on --cuda-device-only -S dat_k_dd.hip -o X.s
 
 function by function (kernels and the device functions they call): the instruction stream, the .amdhsa_*
-descriptor block and the .set resource lines of each symbol.  The order of the functions in the file follows the
+descriptor block and the .set resource lines of each symbol.  The order of the functions in a file follows the
 host code's first use of each template instantiation, so comments, the numbers of local labels (.LBB<fn>_<n>,
 .Lfunc_end<fn>, renumbered here by first appearance within the function) and the __hip_cuid name are dropped.
 
     python tools/same_kernels.py A.s B.s
+    python tools/same_kernels.py A.s --vs B1.s B2.s B3.s
 
-One line per symbol; exit status 1 on any difference or missing symbol.
+A side is the union of its files' symbols.  A symbol that several files of one side hold (an out-of-line device
+function such as build_shared) must be equal in all of them, else it is reported as SPLIT and counts as a
+difference.  One line per symbol; exit status 1 on any difference or missing symbol.
 """
 import re
 import sys
@@ -45,11 +49,30 @@ def functions(path):
     return out
 
 
-a, b = functions(sys.argv[1]), functions(sys.argv[2])
+def side(paths):
+    """the union of the files' symbols, and those that differ between two files of the side"""
+    out, split = {}, set()
+    for p in paths:
+        for sym, fn in functions(p).items():
+            if out.setdefault(sym, fn) != fn:
+                split.add(sym)
+    return out, split
+
+
+args = sys.argv[1:]
+if "--vs" in args:
+    pa, pb = args[:args.index("--vs")], args[args.index("--vs") + 1:]
+else:
+    pa, pb = args[:1], args[1:]
+if not pa or not pb:
+    sys.exit(__doc__)
+(a, sa), (b, sb) = side(pa), side(pb)
 bad = kernels = 0
 for sym in sorted(set(a) | set(b)):
     if sym not in a or sym not in b:
-        verdict, kernel = f"MISSING in {sys.argv[2 if sym in a else 1]}", (a.get(sym) or b.get(sym))[0]
+        verdict, kernel = f"MISSING in {' '.join(pb if sym in a else pa)}", (a.get(sym) or b.get(sym))[0]
+    elif sym in sa or sym in sb:
+        verdict, kernel = f"SPLIT: differs between the files of {' '.join(pa if sym in sa else pb)}", a[sym][0]
     else:
         verdict, kernel = ("equal" if a[sym] == b[sym] else "DIFFERENT"), a[sym][0]
     bad += verdict != "equal"
