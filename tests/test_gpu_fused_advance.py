@@ -41,9 +41,10 @@ FUSED_LAUNCHES = (6, 6)
 SHAPES = [(6, 7), (6, 97), (3, 43), (5, 25), (9, 15), (16, 9), (6, 300)]
 
 
-def _run(n, x0, forests, sf, fused, pipeline=True, mask=None, calls=CALLS, sub=1, log=False, mode="cadmm"):
-    """The run described above.  Returns what the tests compare, the (early, late) advance counts, and (the counts
-    and the stream count after the first call, the launches of (k_advance, k_bucket_scatter) of the whole run)."""
+def _run(n, x0, forests, sf, fused, pipeline=True, mask=None, calls=CALLS, sub=1, log=False, mode="cadmm", ll="pd"):
+    """The run described above, under the low-level law ll.  Returns what the tests compare, the (early, late) advance
+    counts, and (the counts and the stream count after the first call, the launches of (k_advance, k_bucket_scatter)
+    of the whole run)."""
     from distributed_aerial_transportation_amd import BatchedController, scenarios
 
     B = x0.shape[0]
@@ -52,6 +53,7 @@ def _run(n, x0, forests, sf, fused, pipeline=True, mask=None, calls=CALLS, sub=1
         if forests is not None:
             eng.set_forests(forests, sf)
         eng.set_state(x0, np.zeros(B, dtype=np.int32))
+        eng.set_low_level(ll)
         eng.set_sub_batches(sub)
         eng.set_step_pipeline(pipeline)
         eng.set_fused_advance(fused)
@@ -84,10 +86,10 @@ def _run(n, x0, forests, sf, fused, pipeline=True, mask=None, calls=CALLS, sub=1
 
 
 @functools.lru_cache(maxsize=None)
-def _unfused(n, B, forest=True, pipeline=True):
+def _unfused(n, B, forest=True, pipeline=True, ll="pd"):
     """The yardstick, computed once per configuration: the same run with the switch off (the three kernels)."""
     x0, sf = _start(n, B)
-    out, _, (_, _, launches) = _run(n, x0, _forests() if forest else None, sf, False, pipeline)
+    out, _, (_, _, launches) = _run(n, x0, _forests() if forest else None, sf, False, pipeline, ll=ll)
     assert launches == (0, 0)  # the switch off: the three kernels and k_bucket_adv
     return out
 
@@ -102,6 +104,18 @@ def test_shapes_bitwise(n, B):
     assert streams == 4  # the handle's, the tail's, the two pipeline streams: none beyond them
     assert out["env_class0"].max() > 0  # (the forest puts env rows on some scenario)
     _same(out, _unfused(n, B))
+
+
+@pytest.mark.parametrize("n,B", [(6, 97), (5, 25)])
+def test_sm_law_bitwise(n, B):
+    """The "sm" attitude law through k_advance: ll_control_agent's other branch is inlined into k_advance as into
+    k_rollout_agents (the comment at k_low_level), so the fused run gives the bits of the three kernels under it too."""
+    x0, sf = _start(n, B)
+    out, (early, late), (_, _, launches) = _run(n, x0, _forests(), sf, True, ll="sm")
+    assert early + late == B * sum(CALLS) and launches == FUSED_LAUNCHES
+    ref = _unfused(n, B, ll="sm")
+    _same(out, ref)
+    assert not np.array_equal(ref["state1"], _unfused(n, B)["state1"])  # (the law took effect)
 
 
 def test_without_a_forest_every_key_is_class_0():
