@@ -16,7 +16,8 @@ REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "dat_cpu.hip")
 LIB = os.path.join(HERE, "libdat_cpu.so")
 CSRC = os.path.join(REPO, "distributed_aerial_transportation_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("dat_core.hpp", "dat_qp.hpp", "dat_cadmm_step.hpp", "dat_layout.h")]
+# every header under csrc/ (dat_cpu.hip includes them through one another: dat_qp.hpp pulls in dat_ipm.hpp)
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hpp", ".h"))]
 STAMP = LIB + ".srchash"
 D = ctypes.POINTER(ctypes.c_double)
 I = ctypes.POINTER(ctypes.c_int)

@@ -12,8 +12,8 @@ CORE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "distributed_aerial_
 
 
 def build(force=False):
-    deps = [SRC] + [os.path.join(CORE, f)
-                    for f in ("dat_core.hpp", "dat_qp.hpp", "dat_cadmm_step.hpp", "dat_dd_step.hpp", "dat_layout.h")]
+    # every header under csrc/ (hostsim.hip includes them through one another: dat_qp.hpp pulls in dat_ipm.hpp)
+    deps = [SRC] + [os.path.join(CORE, f) for f in sorted(os.listdir(CORE)) if f.endswith((".hpp", ".h"))]
     if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950",
                                SRC, "-o", LIB])

@@ -1,4 +1,4 @@
-"""The IPM's batched LDS reads (dat_qp.hpp "How the IPM reads LDS": records read once per phase, row loops one
+"""The IPM's batched LDS reads (dat_ipm.hpp "How the IPM reads LDS": records read once per phase, row loops one
 slot ahead) in every instantiation the launchers can select.
 
 k_cadmm compiles one IPM loop per (env class, row mode) pair; which pair a scenario runs follows from its env
