@@ -36,6 +36,7 @@ DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(
 MODE_CENTRALIZED, MODE_CADMM, MODE_DD = 0, 1, 2
 QP_OPTIMAL, QP_INACCURATE, QP_INFEASIBLE, QP_FAILED = 0, 1, 2, 3
 LL_KINDS = {"pd": 0, "sm": 1}
+PLANTS = {"rqp": 0, "rp": 1}  # DAT_PLANT_*
 
 
 class DatError(RuntimeError):
@@ -161,6 +162,10 @@ EXPORTS = {
     "dat_rollout": (ctypes.c_int, [H, ctypes.c_int, D]),
     "dat_closed_loop": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_control_steps": (ctypes.c_int, [H, ctypes.c_int, D, D, I, I]),
+    "dat_set_tracking": (ctypes.c_int, [H, D, ctypes.c_int]),
+    "dat_set_clock": (ctypes.c_int, [H, ctypes.c_longlong]),
+    "dat_get_clock": (ctypes.c_int, [H, LL]),
+    "dat_set_plant": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_set_sub_batches": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_set_advance_overlap": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_set_step_pipeline": (ctypes.c_int, [H, ctypes.c_int]),

@@ -242,6 +242,38 @@ class BatchedController:
     def reset_warm_start(self) -> None:
         L.check(self._lib.dat_reset_warm_start(self._h))
 
+    # -- the tracking law, the clock and the plant (dat_set_tracking, dat_set_clock, dat_set_plant)
+    def set_tracking(self, records: Optional[np.ndarray]) -> None:
+        """Select the trajectory-tracking law (tracking.py) wherever the device computes a desired acceleration:
+        records (TRACK_SIZE,) for every scenario or (B, TRACK_SIZE) per scenario; None restores the forest law.
+        Independent of set_forests.  A record the law rejects raises DatError and changes nothing."""
+        if records is None:
+            L.check(self._lib.dat_set_tracking(self._h, None, 0))
+            return
+        rec = L.f64(records)
+        if rec.shape not in ((layout.TRACK_SIZE,), (self.batch, layout.TRACK_SIZE)):
+            raise ValueError(f"set_tracking: records of shape {rec.shape}, expected ({layout.TRACK_SIZE},) or "
+                             f"({self.batch}, {layout.TRACK_SIZE})")
+        L.check(self._lib.dat_set_tracking(self._h, L.ptr(rec), int(rec.ndim == 2)))
+
+    def set_clock(self, clock: int) -> None:
+        """The handle's clock in simulation steps (>= 0): the tracking law's time is clock * dt."""
+        L.check(self._lib.dat_set_clock(self._h, int(clock)))
+
+    @property
+    def clock(self) -> int:
+        """Simulation steps since the handle was made (or set_clock): closed_loop, rollout and rp_rollout advance it."""
+        c = ctypes.c_longlong()
+        L.check(self._lib.dat_get_clock(self._h, ctypes.byref(c)))
+        return c.value
+
+    def set_plant(self, plant: str) -> None:
+        """What closed_loop rolls out: "rqp" (default, the quadrotor-payload system) or "rp" (the rigid payload under
+        the controller's forces; centralized handles, no log)."""
+        if plant not in L.PLANTS:
+            raise NotImplementedError(plant)
+        L.check(self._lib.dat_set_plant(self._h, L.PLANTS[plant]))
+
     # -- state
     def set_state(self, states: np.ndarray, counters: Optional[np.ndarray] = None) -> None:
         states = L.f64(states)

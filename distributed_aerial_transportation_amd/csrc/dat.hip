@@ -178,6 +178,13 @@ struct dat_handle {
   int* pipe_lists = nullptr;  // slist and rlist of the two pipeline streams' drains (4 x B; the handle's stream: slist, rlist)
   double agent_qp_ms = 0.0;  // device time of the last dat_solve_agent_qp_batch launch
   int ll_kind = 0;  // LL_PD (example/rqp_example.py:113) or LL_SM
+  // The tracking law (dat_set_tracking; null: the forest law), the clock (simulation steps since dat_create;
+  // dat_set_clock) and the plant dat_closed_loop rolls out (dat_set_plant).  Settings, like parameters: no
+  // checkpoint carries them.
+  double* track = nullptr;
+  int track_pp = 0;
+  long long clock = 0;
+  int plant = DAT_PLANT_RQP;
   // dat_checkpoint_save / _load: the records' staging buffer and the index lists, grown on demand
   double* ck_stage = nullptr;
   int* ck_list = nullptr;
@@ -354,6 +361,10 @@ KArgs kargs(const dat_handle* h) {
   a.counters = h->counters;
   a.scount = h->scount;
   a.ll_kind = h->ll_kind;
+  a.track = h->track;
+  a.track_pp = h->track_pp;
+  a.tick = h->clock;
+  a.dt = c.dt;
   a.tail_prev = h->nforest > 0 ? TAIL_PREV : INT_MAX;
   a.tail_pass = h->nforest > 0 ? TAIL_PASS : INT_MAX;
   a.route = tail_wanted(h) && h->tail.st;  // (no stream: the wedged scenarios go through k_cadmm's hand-over, same results)
@@ -428,6 +439,7 @@ KArgs sub_kargs(const dat_handle* h, SubRange r, int s) {
 #undef DAT_ARR
   if (a.ppp) a.params += o * a.P;
   a.scen_forest = offp(a.scen_forest, o);
+  if (a.track_pp) a.track = offp(a.track, o * DAT_TRACK_SIZE);
   a.err = offp(a.err, o * err_extent(a.max_iter));
   a.scount = h->scount + SCOUNT_INTS * s;
   return a;
@@ -584,17 +596,21 @@ hipError_t launch_step_rollout(const dat_handle* h, const Sub& u, int mode = ADV
 // tables (Sub::kc_lo / ktab) by it, so a sort reads a key table only behind passes that counted into it.  A pass
 // that is given a table and would not count (the three kernels do not) is an error, not a silently empty list.
 bool fused_ready(const dat_handle* h) { return h->fused_on && h->cfg.mode == DAT_MODE_CADMM && !h->log.open; }
+// u.a.tick is the tick of the step the pass rolls out; the inputs it computes are the next step's and carry that
+// step's tick, one HL period on.
 int launch_advance(const dat_handle* h, const Sub& u, int mode, bool inputs) {
+  Sub nx = u;
+  nx.a.tick = u.a.tick + h->cfg.hl_every;
   if (inputs && mode != ADV_ALL && fused_ready(h)) {
     const int G = 64 / u.a.n;
-    HIPCHK(launch_k_advance(mode, (u.a.B + G - 1) / G, u.st, u.a, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes,
+    HIPCHK(launch_k_advance(mode, (u.a.B + G - 1) / G, u.st, nx.a, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes,
                             (double*)u.a.acc, u.kc_lo, u.kc_hi));
     ++h->n_advance;
     return 0;
   }
   if (inputs && u.kc_lo) return fail("launch_advance: a key table was handed to a pass that runs the three kernels");
   HIPCHK(launch_step_rollout(h, u, mode));
-  if (inputs) HIPCHK(launch_inputs(h, u, mode));
+  if (inputs) HIPCHK(launch_inputs(h, nx, mode));
   return 0;
 }
 
@@ -767,6 +783,7 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
     // the early pass of step k.  It marks adv[], which the rest chain of step k - 1 reads as its gate: after that
     // chain's sort.  With the split forced it also follows the rest drain of step k, for every stamp to be in place.
     side_stream& x = *X[k & 1];
+    base.a.tick = h->clock + (long long)k * h->cfg.hl_every;  // step k's tick (launch_advance: its inputs are step k + 1's)
     Sub early = base;
     early.st = x.st;
     early.a.serial = serial;
@@ -812,6 +829,7 @@ int closed_loop_pipelined(dat_handle* h, int hl_steps) {
     h->cadmm_ms += ms;
   }
   h->hl_steps += hl_steps;
+  h->clock += (long long)hl_steps * h->cfg.hl_every;
   return 0;
 }
 
@@ -1314,6 +1332,7 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
   KArgs a = kargs(h);
   HIPCHK(launch_rollout(a, (int)B, h->stream, steps, h->cfg.dt, (const double*)h->fdes));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->clock += steps;
   return 0;
 }
 
@@ -1333,6 +1352,11 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
 //   pipeline     (pipeline_ready; closed_loop_pipelined) the overlap with the next step's drain split likewise: the
 //                scenarios the early pass has advanced are sorted and drained directly behind it, beside the current
 //                drain's ramp-down, the others after the rest pass.
+// Every launch that computes a desired acceleration carries the tick it is evaluated at (KArgs::tick; the tracking law,
+// dat_set_tracking): step k's is clock + k hl_every, and the passes that compute step k + 1's inputs carry that
+// step's (launch_advance).  The call advances the clock by hl_steps x hl_every.
+// With the rigid-payload plant (dat_set_plant, centralized handles) a step is k_cent and k_rp_advance, which runs the
+// payload's hl_every steps and the next step's desired acceleration, on the serial schedule.
 // What the early pass may touch while the drain runs: a finished scenario's state, acc, env rows / mask, sort key
 // and rotation counter are read by the drain only when a slot takes the scenario (the refill; ksteps == 1 here),
 // so they may be overwritten; its f_des, iters and ipmx were stored write-through before the stamp and are read
@@ -1341,6 +1365,9 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
 // the k_cadmm launch spans (S launches per HL step: dat_get_kernel_ms / (hl_steps S) is one launch).
 int dat_closed_loop(dat_handle* h, int hl_steps) {
   if (!h) return fail("null handle");
+  const bool rp = h->plant == DAT_PLANT_RP;
+  if (rp && h->log.open)
+    return fail("dat_closed_loop: the log does not record the rigid-payload plant (DAT_PLANT_RP) yet: close the log");
   if (log_admit(h, hl_steps) || step_entry(h)) return -1;
   const int S = h->nsub;
   if (hl_steps > 0) h->env_sub = S;
@@ -1367,7 +1394,15 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
         v.ek = h->sub_ev[2 * ((size_t)k * S + s)];
         v.e1 = h->sub_ev[2 * ((size_t)k * S + s) + 1];
       }
-      if (!overlap) {
+      v.a.tick = h->clock + (long long)k * h->cfg.hl_every;
+      if (rp) {  // k_cent, then the payload's steps and the next step's desired acceleration in one launch
+        if (k == 0) HIPCHK(launch_inputs(h, v, ADV_ALL, IN_DESIRED));
+        if (launch_step(h, v, S == 1)) return -1;
+        KArgs nx = v.a;
+        nx.tick = v.a.tick + h->cfg.hl_every;
+        HIPCHK(launch_k_rp_advance(v.st, nx, h->cfg.hl_every, h->cfg.dt, (const double*)v.a.fdes,
+                                   k + 1 < hl_steps ? (double*)v.a.acc : nullptr));
+      } else if (!overlap) {
         HIPCHK(launch_inputs(h, v, ADV_ALL, IN_DESIRED));
         if (launch_step(h, v, S == 1)) return -1;
         HIPCHK(launch_step_rollout(h, v));
@@ -1405,6 +1440,60 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
     h->marks.push_back(now_ms());
   }
   HIPCHK(hipStreamSynchronize(h->stream));
+  if (hl_steps > 0) h->clock += (long long)hl_steps * h->cfg.hl_every;
+  return 0;
+}
+
+// ---- the tracking law, the clock and the plant ------------------------------------------------------------------
+int dat_set_tracking(dat_handle* h, const double* rec, int per_scenario) {
+  if (!h) return fail("dat_set_tracking: null handle");
+  const size_t count = per_scenario ? (size_t)h->cfg.batch : 1;
+  if (rec) {  // checked on the host before anything is copied or launched
+    static const char* const names[DAT_TRACK_SIZE] = {"CX", "CY", "RADIUS", "HEIGHT", "FREQ", "T0", "KP", "KV",
+                                                      "AMAX", "WAMP", "WZ", "reserved"};
+    for (size_t k = 0; k < count; ++k) {
+      const int bad = track_record_bad_field(rec + k * DAT_TRACK_SIZE);
+      if (bad >= 0)
+        return fail("dat_set_tracking: record " + std::to_string(k) + ": field " + names[bad] + " = " +
+                    std::to_string(rec[k * DAT_TRACK_SIZE + bad]) +
+                    " (every field must be finite; RADIUS, FREQ, KP, KV >= 0); the law in force is unchanged");
+    }
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipStream_t s : h->streams) HIPCHK(hipStreamSynchronize(s));
+  double* fresh = nullptr;
+  if (rec) {
+    if (dalloc(h, &fresh, count * DAT_TRACK_SIZE)) return -1;
+    HIPCHK(hipMemcpyAsync(fresh, rec, sizeof(double) * count * DAT_TRACK_SIZE, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  dfree(h, h->track);
+  h->track = fresh;
+  h->track_pp = rec && per_scenario ? 1 : 0;
+  return 0;
+}
+
+int dat_set_clock(dat_handle* h, long long clock) {
+  if (!h) return fail("dat_set_clock: null handle");
+  if (clock < 0) return fail("dat_set_clock: negative clock " + std::to_string(clock) + " (simulation steps, >= 0)");
+  h->clock = clock;
+  return 0;
+}
+
+int dat_get_clock(dat_handle* h, long long* clock) {
+  if (!h || !clock) return fail("dat_get_clock: null argument");
+  *clock = h->clock;
+  return 0;
+}
+
+int dat_set_plant(dat_handle* h, int plant) {
+  if (!h) return fail("dat_set_plant: null handle");
+  if (plant != DAT_PLANT_RQP && plant != DAT_PLANT_RP) return fail("dat_set_plant: bad plant " + std::to_string(plant));
+  if (plant == DAT_PLANT_RP && h->cfg.mode != DAT_MODE_CENTRALIZED)
+    return fail("dat_set_plant: the rigid-payload plant (DAT_PLANT_RP) runs on centralized handles only");
+  if (plant == DAT_PLANT_RP && h->log.open)
+    return fail("dat_set_plant: the log does not record the rigid-payload plant (DAT_PLANT_RP) yet: close the log");
+  h->plant = plant;
   return 0;
 }
 
@@ -1798,6 +1887,7 @@ int dat_rp_rollout(dat_handle* h, int steps, const double* f) {
   KArgs a = kargs(h);
   HIPCHK(launch_k_rp_rollout(h->stream, a, steps, h->cfg.dt, (const double*)h->fdes));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->clock += steps;
   return 0;
 }
 
@@ -1862,6 +1952,8 @@ int dat_pmrl_forward(dat_handle* h, const double* f, double* ddq, double* dvl, d
 int dat_log_begin(dat_handle* h, const int* scenarios, int count, int log_every, int hl_capacity, int summary) {
   if (!h) return fail("null handle");
   if (h->log.open) return fail("dat_log_begin: a log is already open (dat_log_end first)");
+  if (h->plant == DAT_PLANT_RP)
+    return fail("dat_log_begin: the log does not record the rigid-payload plant (DAT_PLANT_RP) yet");
   const int B = h->cfg.batch, n = h->cfg.n;
   if (count < 0 || count > B) return fail("dat_log_begin: count must be in [0, batch]");
   if (!scenarios && count != 0 && count != B)

@@ -439,9 +439,15 @@ __device__ __forceinline__ bool rollout_lanes(const KArgs& a, int steps, double 
         for (int c = 0; c < 3; ++c) r[3 * i + c] = fd[c];
         ri[2 + i] = a.qstatus[(size_t)sc * n + i];
         if (i == 0) {
-          double m[DAT_MOUNTAIN_SIZE], ref[6];  // x_ref, v_ref
-          mountain_of(a, sc, m);
-          forest_references(xl, m, REF_X_OFFSET, ref, ref + 3);
+          double ref[6];  // x_ref, v_ref of the law in force at the HL instant
+          if (a.track) {
+            double ar[3];
+            track_references(track_of(a, sc), track_time(a.tick, a.dt), ref, ref + 3, ar);
+          } else {
+            double m[DAT_MOUNTAIN_SIZE];
+            mountain_of(a, sc, m);
+            forest_references(xl, m, REF_X_OFFSET, ref, ref + 3);
+          }
           r[DAT_LOG_HL_MIND(n)] = a.mind[sc];
           for (int c = 0; c < 6; ++c) r[DAT_LOG_HL_XREF(n) + c] = lref[6 * ls + c] = ref[c];
           ri[0] = a.iters[sc];
@@ -564,6 +570,62 @@ __global__ void k_rp_rollout(KArgs a, int steps, double dt, const double* f) {
   int cnt = a.counter[sc];
   for (int s = 0; s < steps; ++s) rp_step(prm, n, st, &cnt, f + (size_t)sc * 3 * n, dt);
   a.counter[sc] = cnt;
+}
+
+__device__ __forceinline__ void desired_of(const KArgs& a, int sc, double* acc);  // (below, with k_desired)
+// The rigid payload's advance pass of the resident closed loop (dat_set_plant DAT_PLANT_RP): the `steps` payload steps
+// of an HL period under the forces k_cent has just published, k_rp_rollout's mapping (one lane per scenario), with the
+// payload's state in registers, then the next step's desired acceleration (desired_of's two laws, at the launch's
+// tick: the next step's) from those registers.  rp_step's pieces, in its order, so a step is rp_step's to the bit.
+__global__ __launch_bounds__(64) void k_rp_advance(KArgs a, int steps, double dt, const double* f, double* acc) {
+  const int sc = blockIdx.x * blockDim.x + threadIdx.x;
+  if (sc >= a.B) return;
+  const int n = a.n;
+  const double* prm = prm_of(a, sc);
+  double* g = a.state + (size_t)sc * a.S;
+  const double* fs = f + (size_t)sc * 3 * n;
+  double xl[3], vl[3], Rl[9], wl[3];
+  for (int c = 0; c < 3; ++c) {
+    xl[c] = g[DAT_S_XL(n) + c];
+    vl[c] = g[DAT_S_VL(n) + c];
+    wl[c] = g[DAT_S_WL(n) + c];
+  }
+  for (int k = 0; k < 9; ++k) Rl[k] = g[DAT_S_RL(n) + k];
+  int cnt = a.counter[sc];
+  const double ml = prm[DAT_P_MT];
+  const double* r = prm + DAT_P_RCOM(n);
+  // the force sum does not change while the forces are held
+  double F[3] = {0, 0, 0};
+  for (int i = 0; i < n; ++i)
+    for (int c = 0; c < 3; ++c) F[c] += fs[3 * i + c];
+  const double dvl[3] = {F[0] / ml, F[1] / ml, F[2] / ml - DAT_GRAVITY};
+  for (int s = 0; s < steps; ++s) {
+    double Mo[3] = {0, 0, 0}, dwl[3];
+    for (int i = 0; i < n; ++i) {
+      double fi[3] = {fs[3 * i], fs[3 * i + 1], fs[3 * i + 2]}, fb[3], m3[3];
+      mtv3(Rl, fi, fb);
+      cross3(r + 3 * i, fb, m3);
+      for (int c = 0; c < 3; ++c) Mo[c] += m3[c];
+    }
+    rot_accel(prm + DAT_P_JT, prm + DAT_P_JTI, wl, Mo, dwl);
+    integrate_lin(xl, vl, dvl, dt);
+    integrate_rot(Rl, wl, dwl, dt);
+    if (projection_due(&cnt)) polar3(Rl);
+  }
+  for (int c = 0; c < 3; ++c) {
+    g[DAT_S_XL(n) + c] = xl[c];
+    g[DAT_S_VL(n) + c] = vl[c];
+    g[DAT_S_WL(n) + c] = wl[c];
+  }
+  for (int k = 0; k < 9; ++k) g[DAT_S_RL(n) + k] = Rl[k];
+  a.counter[sc] = cnt;
+  if (acc == nullptr) return;  // (the call's last step: the next call computes its own inputs)
+  double* o = acc + (size_t)sc * 6;
+  if (a.track) {
+    desired_accel_track_at(xl, vl, track_of(a, sc), track_time(a.tick, a.dt), o);
+  } else {
+    desired_of(a, sc, acc);  // the forest law reads a state block: the one this lane has just stored
+  }
 }
 
 // Point-mass rigid-link system (PMRLDynamics, system/point_mass_rigid_link.py:135-254; the pieces of
@@ -694,10 +756,15 @@ __global__ __launch_bounds__(64) void k_pmrl_forward(KArgs a, const double* f, d
   }
 }
 
-// the desired acceleration of scenario sc from its state in memory (k_desired, k_advance)
+// the desired acceleration of scenario sc from its state in memory (k_desired, k_advance): the tracking law at the
+// launch's tick where records are set (uniform per launch), else the forest law
 __device__ __forceinline__ void desired_of(const KArgs& a, int sc, double* acc) {
   const double* st = a.state + (size_t)sc * a.S;
   double* o = acc + (size_t)sc * 6;
+  if (a.track) {
+    desired_accel_track(st, a.n, track_of(a, sc), track_time(a.tick, a.dt), o);
+    return;
+  }
   double m[DAT_MOUNTAIN_SIZE];
   mountain_of(a, sc, m);
   desired_accel_forest(st, a.n, m, REF_X_OFFSET, o);
@@ -949,6 +1016,10 @@ hipError_t launch_k_low_level(hipStream_t st, const KArgs& a, const double* fdes
 }
 hipError_t launch_k_rp_rollout(hipStream_t st, const KArgs& a, int steps, double dt, const double* f) {
   hipLaunchKernelGGL(k_rp_rollout, dim3((a.B + 63) / 64), dim3(64), 0, st, a, steps, dt, f);
+  return hipGetLastError();
+}
+hipError_t launch_k_rp_advance(hipStream_t st, const KArgs& a, int steps, double dt, const double* f, double* acc) {
+  hipLaunchKernelGGL(k_rp_advance, dim3((a.B + 63) / 64), dim3(64), 0, st, a, steps, dt, f, acc);
   return hipGetLastError();
 }
 hipError_t launch_k_pmrl_rollout(int blocks, hipStream_t st, const KArgs& a, int steps, int nf, double dt,

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "dat_cadmm_step.hpp"
+#include "dat_track.hpp"
 
 namespace dat {
 
@@ -131,6 +132,13 @@ struct KArgs {
   int* qempty;                   // one word of mapped host memory: serial, once k_cadmm's class-0 queue is claimed empty
   const unsigned char* advmask;  // dat_debug_advance_split: a done stamp counts only where the mask is set (null: all)
   unsigned long long* advcnt;    // scenario-steps advanced by the [0] early, [1] rest pass
+  // The tracking law (dat_set_tracking; track null: the forest law) and the handle's clock.
+  const double* track;           // tracking records (DAT_TRACK_SIZE doubles each), per scenario (track_pp) or one for all
+  int track_pp;
+  long long tick;                // the simulation step at which this launch's desired acceleration (and the logging
+                                 // rollout's x_ref / v_ref) is evaluated: t = tick dt.  An advance pass of step k
+                                 // computes the inputs of step k + 1 and carries that step's tick.
+  double dt;
 };
 
 // Modes of the gated kernels (k_rollout_agents, k_desired, k_env_class): which scenarios of the grid take part
@@ -184,6 +192,11 @@ __device__ inline int wave_max(int v) {
 }
 
 __device__ inline const double* prm_of(const KArgs& a, int sc) { return a.params + (a.ppp ? (size_t)sc * a.P : 0); }
+
+// scenario sc's tracking record (a.track set)
+__device__ inline const double* track_of(const KArgs& a, int sc) {
+  return a.track + (a.track_pp ? (size_t)sc * DAT_TRACK_SIZE : 0);
+}
 
 __device__ inline void forest_of(const KArgs& a, int sc, const double** trees, int* nt) {
   *trees = nullptr;

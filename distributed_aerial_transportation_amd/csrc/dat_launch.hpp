@@ -114,6 +114,8 @@ hipError_t launch_k_advance(int adv, int blocks, hipStream_t st, const KArgs& a,
                             const double* fdes, double* acc, int* kc_lo, int* kc_hi);
 hipError_t launch_k_low_level(hipStream_t st, const KArgs& a, const double* fdes, double* fo, double* Mo);
 hipError_t launch_k_rp_rollout(hipStream_t st, const KArgs& a, int steps, double dt, const double* f);
+// acc: where the next step's desired acceleration goes (a.tick: that step's), or null: none
+hipError_t launch_k_rp_advance(hipStream_t st, const KArgs& a, int steps, double dt, const double* f, double* acc);
 hipError_t launch_k_pmrl_rollout(int blocks, hipStream_t st, const KArgs& a, int steps, int nf, double dt,
                                  const double* f);
 hipError_t launch_k_pmrl_forward(int blocks, hipStream_t st, const KArgs& a, const double* f, double* ddq, double* dvl,

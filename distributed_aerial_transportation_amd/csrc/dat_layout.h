@@ -71,6 +71,23 @@
 #define DAT_M_DEPTH 4
 #define DAT_MOUNTAIN_SIZE 5
 
+// ---- tracking record (DAT_TRACK_SIZE doubles; dat_set_tracking, the law: dat_track.hpp) ----------------------
+// test/control/test_rqpcontrollers.py:24-48, test/control/test_rpcentralized.py:14-38: the reference flies centre
+// (0, 0), radius 1, height 1, 0.5 rad/s, T0 = 0, gains 1 and 1, no clamp, dwl_des = (sin t, cos t, pi / 12)
+#define DAT_T_CX 0
+#define DAT_T_CY 1
+#define DAT_T_RADIUS 2
+#define DAT_T_HEIGHT 3
+#define DAT_T_FREQ 4         // angular rate, rad/s
+#define DAT_T_T0 5           // time offset, s
+#define DAT_T_KP 6
+#define DAT_T_KV 7
+#define DAT_T_AMAX 8         // clamp on |dvl_des|; <= 0: none
+#define DAT_T_WAMP 9         // dwl_des = (WAMP sin tau, WAMP cos tau, WZ)
+#define DAT_T_WZ 10
+#define DAT_T_RESERVED 11    // zero
+#define DAT_TRACK_SIZE 12
+
 // ---- records of the closed loop's log (dat_log_*), in 8-byte words, laid out [record][slot][word] --------
 // HL record (after control step k): f_des (3n, agent-major), min_env_dist, x_ref (3), v_ref (3), then 32-bit
 // ints packed two per word: iters, collision, qp_status (n), padded to a whole word.

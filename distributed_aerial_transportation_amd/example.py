@@ -23,11 +23,12 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import layout, scenarios
+from . import layout, scenarios, tracking
 from .env_forest import Forest
 from .system import RQPState, pack_state
 
 CONTROLLER_TYPES = ("centralized", "dual-decomposition", "consensus-admm")
+LAWS = ("forest", "circle")
 
 
 @dataclass
@@ -145,7 +146,8 @@ def _simulate_resident(eng, headers: List[dict], n: int, hl_steps: int, log_freq
 def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scenario_forest=None, n: int = 3,
                    T: float = 100.0, dt: float = 1e-3, hl_rel_freq: int = 10, log_freq: Optional[int] = None,
                    so3_controller_type: str = "pd", params: Optional[np.ndarray] = None, device: int = 0,
-                   progress: bool = False, resident: bool = False, record=None, chunk_hl: int = 100) -> List[dict]:
+                   progress: bool = False, resident: bool = False, record=None, chunk_hl: int = 100,
+                   law: str = "forest", track: Optional[np.ndarray] = None) -> List[dict]:
     """B closed loops of example/rqp_example.py:main on one GPU; states (B, 12n + 18) (packed
     RQPState), forests[scenario_forest[b]] the forest of scenario b.  Returns one logs dict per scenario.
 
@@ -153,11 +155,18 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
     in HBM (dat_log_*): nothing is copied per step, the records are read every chunk_hl HL steps.  record: the
     scenarios whose dicts are returned (strictly increasing indices; default all).  The resident loop runs whole
     HL periods: a step count that is no multiple of hl_rel_freq raises ValueError.  The default (resident=False)
-    drives the loop from the host step by step and returns every scenario's dict."""
+    drives the loop from the host step by step and returns every scenario's dict.
+
+    law: "forest" (example/rqp_example.py:33-59) or "circle", the reference's trajectory-tracking law
+    (test/control/test_rqpcontrollers.py:24-48; tracking.py) at t = i dt, with `track` its records ((TRACK_SIZE,) or
+    (B, TRACK_SIZE); default the reference's circle); forests may then be empty.  Both paths honour it, and the logs'
+    x_err_seq / v_err_seq are taken against the law's own references."""
     from .control import BatchedController
 
     if controller_type not in CONTROLLER_TYPES:
         raise NotImplementedError(controller_type)
+    if law not in LAWS:
+        raise NotImplementedError(law)
     log_freq = hl_rel_freq if log_freq is None else log_freq
     states = np.atleast_2d(np.asarray(states, float))
     B = states.shape[0]
@@ -167,13 +176,20 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
         raise ValueError(f"resident=True runs whole HL periods: {len(np.arange(0, T, dt))} steps (T / dt) is no "
                          f"multiple of hl_rel_freq = {hl_rel_freq}")
     eng = BatchedController(controller_type, n, B, prm, dt=dt, hl_every=hl_rel_freq, device=device)
-    eng.set_forests(forests, sf)
+    eng.set_forests(forests, sf if forests else None)
+    rec = None
+    if law == "circle":
+        rec = tracking.circle_record() if track is None else np.asarray(track, float)
+        eng.set_tracking(rec)
+    elif not forests:
+        raise ValueError('law="forest" needs the forests its references are taken from')
+    trees = [(forests[sf[b]].num_trees, forests[sf[b]].tree_pos) if forests else (0, np.zeros((0, 3))) for b in range(B)]
     eng.set_low_level(so3_controller_type)
     eng.set_state(states, np.zeros(B, dtype=np.int32))
     steps = len(np.arange(0, T, dt))  # t_seq = np.arange(0, T, dt) (:107)
     if resident:
         headers = [dict(n=n, dt=dt, T=T, hl_rel_freq=hl_rel_freq, log_freq=log_freq,
-                        num_trees=forests[sf[b]].num_trees, tree_pos=forests[sf[b]].tree_pos,
+                        num_trees=trees[b][0], tree_pos=trees[b][1],
                         controller_type=controller_type) for b in range(B)]
         try:
             return _simulate_resident(eng, headers, n, steps // hl_rel_freq, log_freq, record, chunk_hl, hl_rel_freq,
@@ -181,7 +197,7 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
         finally:
             eng.close()
     logs = [dict(n=n, dt=dt, T=T, hl_rel_freq=hl_rel_freq, log_freq=log_freq,
-                 num_trees=forests[sf[b]].num_trees, tree_pos=forests[sf[b]].tree_pos, controller_type=controller_type,
+                 num_trees=trees[b][0], tree_pos=trees[b][1], controller_type=controller_type,
                  state_seq=[], x_err_seq=[], v_err_seq=[], f_des_seq=[], iter_seq=[], solve_time_seq=[],
                  min_env_dist_seq=[], w_seq=[]) for b in range(B)]
     x_ref = v_ref = None
@@ -191,9 +207,12 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
             x, _ = eng.get_state()
             x_ref = np.empty((B, 3))
             v_ref = np.empty((B, 3))
-            for f in np.unique(sf):
-                idx = np.nonzero(sf == f)[0]
-                x_ref[idx], v_ref[idx] = references(x[idx, 12 * n:12 * n + 3], forests[f])
+            if rec is not None:  # the tracked references at the HL instant (the device's clock reads i)
+                x_ref[:], v_ref[:], _ = tracking.references(rec, i * dt)
+            else:
+                for f in np.unique(sf):
+                    idx = np.nonzero(sf == f)[0]
+                    x_ref[idx], v_ref[idx] = references(x[idx, 12 * n:12 * n + 3], forests[f])
             r = eng.control(None, None)  # desired acceleration on device (:102-103), then control (:104)
             for b in range(B):
                 lg = logs[b]
@@ -227,16 +246,18 @@ def simulate_batch(controller_type: str, states: np.ndarray, forests: list, scen
 
 def simulate(controller_type: str = "dual-decomposition", n: int = 3, T: float = 100.0, dt: float = 1e-3,
              hl_rel_freq: int = 10, log_freq: Optional[int] = None, env=None, state: Optional[RQPState] = None,
-             so3_controller_type: str = "pd", device: int = 0, verbose: bool = True, resident: bool = False) -> dict:
+             so3_controller_type: str = "pd", device: int = 0, verbose: bool = True, resident: bool = False,
+             law: str = "forest", track: Optional[np.ndarray] = None) -> dict:
     """example/rqp_example.py:main on the GPU for one scenario (rqp_setup(n) start state, Forest()
     environment -- pass env = Forest.seeded(s) for a reproducible layout); prints the statistics of
-    :140 and returns the logs dict of :141-165.  resident: as in simulate_batch."""
-    env = Forest() if env is None else env
+    :140 and returns the logs dict of :141-165.  resident, law, track: as in simulate_batch; under law="circle" no
+    forest is made unless env is given."""
+    forests = [Forest() if env is None else env] if law == "forest" or env is not None else []
     if state is None:
         _, _, state = scenarios.rqp_setup(n)
-    logs = simulate_batch(controller_type, pack_state(state)[None], [env], None, n=n, T=T, dt=dt,
+    logs = simulate_batch(controller_type, pack_state(state)[None], forests, None, n=n, T=T, dt=dt,
                           hl_rel_freq=hl_rel_freq, log_freq=log_freq, so3_controller_type=so3_controller_type,
-                          device=device, resident=resident)[0]
+                          device=device, resident=resident, law=law, track=track)[0]
     if verbose:
         print_stats(logs["iter_seq"], logs["solve_time_seq"])
     return logs

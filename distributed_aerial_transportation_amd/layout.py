@@ -37,6 +37,8 @@ def fn(name: str, n: int) -> int:
 
 P = {k[len("DAT_P_"):]: const(k) for k in _const if k.startswith("DAT_P_")}
 M = {k[len("DAT_M_"):]: const(k) for k in _const if k.startswith("DAT_M_")}
+T = {k[len("DAT_T_"):]: const(k) for k in _const if k.startswith("DAT_T_")}  # tracking record (dat_set_tracking)
+TRACK_SIZE = const("DAT_TRACK_SIZE")
 NENV = const("DAT_NENV")
 GRAVITY = const("DAT_GRAVITY")
 

@@ -177,5 +177,59 @@ class RPDynamics:
         return s
 
 
-__all__ = ["RPParameters", "RPState", "RPCollision", "rp_setup", "rp_equilibrium_forces", "pack_rp_params",
+class RPClosedLoop:
+    """The loop of test/control/test_rpcentralized.py:41-62 resident on the device: per step the tracking law at
+    t = clock * dt (tracking.py; ``track``: one record or one per scenario, default the reference's circle),
+    RPCentralizedController.control (k_cent, prev_f held on a non-OPTIMAL solve) and RPDynamics.integrate, the last
+    two with the next step's law in one launch (k_rp_advance).  ``states``: one RPState or a list of B of them;
+    ``run(steps)`` advances every scenario by `steps` control steps with nothing copied per step."""
+
+    def __init__(self, params: RPParameters, state, dt: float, track: Optional[np.ndarray] = None,
+                 hl_every: int = 1, device: int = 0) -> None:
+        from . import tracking
+        from .control import BatchedController
+
+        states = [state] if isinstance(state, RPState) else list(state)
+        self.params, self.dt, self.n, self.batch = params, dt, params.n, len(states)
+        self._eng = BatchedController("centralized", self.n, self.batch, pack_rp_params(params), dt=dt,
+                                      hl_every=hl_every, device=device)
+        self._eng.set_plant("rp")
+        self._eng.set_tracking(tracking.circle_record() if track is None else track)
+        self._eng.set_state(np.stack([pack_rp_state(s, self.n) for s in states]),
+                            np.array([s.counter for s in states], dtype=np.int32))
+
+    def run(self, steps: int) -> None:
+        self._eng.closed_loop(int(steps))
+
+    @property
+    def clock(self) -> int:
+        return self._eng.clock
+
+    def set_clock(self, clock: int) -> None:
+        self._eng.set_clock(clock)
+
+    @property
+    def states(self) -> list:
+        x, c = self._eng.get_state()
+        out = []
+        for b in range(self.batch):
+            s = unpack_rp_state(x[b], self.n)
+            s.counter = int(c[b])
+            out.append(s)
+        return out
+
+    @property
+    def state(self) -> RPState:
+        return self.states[0]
+
+    @property
+    def f(self) -> np.ndarray:
+        """The forces of the last control step, (B, 3, n) (the checkpoint records' f_des)."""
+        return self._eng.checkpoint().arrays()["f_des"].transpose(0, 2, 1).copy()
+
+    def close(self) -> None:
+        self._eng.close()
+
+
+__all__ = ["RPClosedLoop", "RPParameters", "RPState", "RPCollision", "rp_setup", "rp_equilibrium_forces", "pack_rp_params",
            "pack_rp_state", "unpack_rp_state", "RPCentralizedController", "RPDynamics"]

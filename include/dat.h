@@ -104,7 +104,8 @@ int dat_get_state(dat_handle* h, double* state, int* counters);
  * applies (f_des) and the previous step's pass count and slowest IPM count, from which the kernels take the IPM
  * start regime, the drain order and the tail rule.  A checkpoint record is all of that for one scenario
  * (csrc/dat_layout.h, DAT_CK_*); a blob is a header of DAT_CK_HEADER_BYTES and `count` records.  Parameters,
- * forests, tolerances, schedule switches, work counters, the log and a step's outputs (qp_status, min_env_dist,
+ * forests, the clock and the tracking records (dat_set_clock, dat_set_tracking: handle settings, like parameters),
+ * tolerances, schedule switches, work counters, the log and a step's outputs (qp_status, min_env_dist,
  * collision, err_seq) are not part of it.  A scenario's arithmetic depends on neither its batch, its slot nor the
  * schedule, so a record restored into any slot of any handle of the same mode and n (with the same parameters,
  * forest and settings) continues bitwise as the scenario it was taken from.
@@ -192,6 +193,37 @@ int dat_pmrl_forward(dat_handle* h, const double* f, double* ddq, double* dvl, d
  * acceleration of :33-59): hl_steps x (desired acceleration + control step +
  * hl_every rollout steps); inputs already in HBM, nothing copied per step. */
 int dat_closed_loop(dat_handle* h, int hl_steps);
+
+/* ---- the trajectory-tracking law, the clock and the plant of the resident loop ------------------------------------
+ * The reference has a second desired-acceleration law beside the forest law: the time-dependent tracking law its
+ * controllers fly without a forest (test/control/test_rqpcontrollers.py:24-48 _desired_acceleration_noenv,
+ * test/control/test_rpcentralized.py:14-38): a circle of radius 1 m at 1 m height, 0.5 rad/s, with feed-forward
+ * a_ref, no clamp, and dwl_des = (sin t, cos t, pi / 12).  csrc/dat_track.hpp states it once, for the kernels and the
+ * host; a scenario's tracking record (DAT_TRACK_SIZE doubles, csrc/dat_layout.h DAT_T_*) holds centre, radius,
+ * height, angular rate, time offset T0, gains KP / KV, the clamp AMAX on |dvl_des| (<= 0: none) and dwl_des's
+ * amplitude and z component.
+ *
+ * dat_set_tracking: rec = NULL restores the forest law; otherwise one record (per_scenario = 0) or B records select
+ * the tracking law wherever the device computes a desired acceleration (dat_control_step with acc_des = NULL,
+ * dat_closed_loop) and for the log's x_ref / v_ref.  Independent of dat_set_forests: env rows stay active.  A
+ * non-finite field, RADIUS < 0, FREQ < 0, KP < 0 or KV < 0 is rejected on the host, nothing copied or launched.
+ *
+ * The clock: simulation steps since dat_create (dat_set_clock to place it; negative: an error).  dat_closed_loop
+ * advances it by hl_steps x hl_every, dat_rollout and dat_rp_rollout by `steps`; dat_control_step evaluates the law
+ * at the current clock, t = clock x dt (the reference's t_seq[i] = i dt), and does not advance it.  Clock and records
+ * are handle settings, like parameters: checkpoints carry neither.
+ *
+ * dat_set_plant: what dat_closed_loop rolls out.  DAT_PLANT_RQP (default): the quadrotor-payload system.
+ * DAT_PLANT_RP: the rigid payload under the controller's forces (RPDynamics.integrate,
+ * system/rigid_payload.py:93-130), centralized handles only: hl_steps x (k_cent, k_rp_advance), the resident form of
+ * test/control/test_rpcentralized.py:41-62 (there hl_every = 1, dt = 10 ms).  The recorder does not know the RP
+ * plant yet: with a log open DAT_PLANT_RP is an error, and so is dat_log_begin under it. */
+#define DAT_PLANT_RQP 0
+#define DAT_PLANT_RP 1
+int dat_set_tracking(dat_handle* h, const double* rec, int per_scenario);
+int dat_set_clock(dat_handle* h, long long clock);
+int dat_get_clock(dat_handle* h, long long* clock);
+int dat_set_plant(dat_handle* h, int plant);
 /* C-ADMM handles: run dat_closed_loop on `count` (1..4) contiguous sub-batches of the scenarios, each on
  * its own stream with no synchronisation between sub-batches or steps, so that one sub-batch's kernels
  * fill the others' drain tails and short kernels.  Per scenario the arithmetic is unchanged (a scenario's
