@@ -61,6 +61,19 @@ class Config(ctypes.Structure):
     ]
 
 
+class EpisodeRules(ctypes.Structure):
+    """dat_episode_rules (include/dat.h)"""
+
+    _fields_ = [
+        ("goal_x", ctypes.c_double),
+        ("bound", ctypes.c_double),
+        ("max_steps", ctypes.c_int),
+        ("stall_steps", ctypes.c_int),
+        ("on_collision", ctypes.c_int),
+        ("wrap", ctypes.c_int),
+    ]
+
+
 def source_hash() -> str:
     """sha256 of the library's sources (the build stamp next to libdat.so records the one it was built from)."""
     h = hashlib.sha256()
@@ -207,6 +220,15 @@ EXPORTS = {
     "dat_log_read_summary": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int, I, D, U8]),
     "dat_log_clear": (ctypes.c_int, [H]),
     "dat_log_end": (ctypes.c_int, [H]),
+    "dat_episode_default_rules": (None, [ctypes.POINTER(EpisodeRules)]),
+    "dat_episode_begin": (ctypes.c_int, [H, ctypes.POINTER(EpisodeRules), ctypes.c_void_p, ctypes.c_longlong,
+                                         ctypes.c_int]),
+    "dat_episode_counts": (ctypes.c_int, [H, LL, LL, LL, LL]),
+    "dat_episode_read": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int, I, I, I, I, LL, LL, I, I, I, I, I, D, D, D]),
+    "dat_episode_clear": (ctypes.c_int, [H]),
+    "dat_episode_end": (ctypes.c_int, [H]),
+    "dat_episode_slots": (ctypes.c_int, [H, I, I, I, I]),
+    "dat_get_episode_respawns": (ctypes.c_int, [H, LL, LL, LL]),
     "dat_comm_unique_id": (ctypes.c_int, [U8]),
     "dat_comm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, U8, ctypes.POINTER(H)]),
     "dat_comm_destroy": (ctypes.c_int, [H]),

@@ -461,6 +461,90 @@ class BatchedController:
     def closed_loop(self, hl_steps: int) -> None:
         L.check(self._lib.dat_closed_loop(self._h, int(hl_steps)))
 
+    # -- episodes (dat_episode_*): scenarios end and respawn from a pool inside closed_loop
+    def episodes_begin(self, pool=None, goal_x: Optional[float] = None, max_steps: int = 0, stall_steps: int = 0,
+                       on_collision: bool = True, bound: Optional[float] = None, wrap: bool = True,
+                       capacity: Optional[int] = None) -> None:
+        """Open episodes: from now on closed_loop ends a scenario's episode, after its control step and before its
+        rollout, for the lowest reason that fires -- DIVERGED (a non-finite word of xl / vl, or max |xl_c| > bound),
+        COLLISION (on_collision), GOAL (xl_x >= goal_x), STALL (stall_steps consecutive control steps at
+        max_iter + 1 passes; not on centralized handles), TIME_LIMIT (max_steps control steps) -- records the outcome
+        and overwrites the scenario with a record of `pool` instead of rolling it out.  pool: a Checkpoint (or a
+        blob's bytes) of P records, uploaded once; None: a checkpoint of the whole batch taken now.  Slot s first
+        runs record s mod P (loaded here), then (s + j B) mod P for its j-th respawn; with wrap=False a slot whose
+        next index would reach P goes idle (it runs on and records nothing further).  capacity: outcome records the
+        table holds (default 4 x batch).  control and rollout do not evaluate episodes.  Not with a log, the "rp"
+        plant or tracking records; restore raises while episodes are open."""
+        ck = self.checkpoint() if pool is None else pool
+        data = ck._buf if isinstance(ck, Checkpoint) else np.frombuffer(bytes(ck), dtype=np.uint8)
+        r = L.EpisodeRules()
+        self._lib.dat_episode_default_rules(r)
+        if goal_x is not None:
+            r.goal_x = float(goal_x)
+        if bound is not None:
+            r.bound = float(bound)
+        r.max_steps, r.stall_steps = int(max_steps), int(stall_steps)
+        r.on_collision, r.wrap = int(bool(on_collision)), int(bool(wrap))
+        cap = 4 * self.batch if capacity is None else int(capacity)
+        L.check(self._lib.dat_episode_begin(self._h, r, data.ctypes.data_as(ctypes.c_void_p), data.size, cap))
+
+    def episodes_counts(self) -> dict:
+        """ended: episodes ended per reason since episodes_begin (a dict by reason name, and "total"); held: records
+        in the table; lost: records dropped beyond its capacity since the last episodes_clear; idle: idle slots."""
+        e = np.zeros(layout.EP_NREASON, dtype=np.int64)
+        h, lo, i = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(self._lib.dat_episode_counts(self._h, L.ptr(e, L.LL), ctypes.byref(h), ctypes.byref(lo),
+                                             ctypes.byref(i)))
+        ended = {k: int(e[v]) for k, v in layout.EP_REASONS.items() if v}
+        ended["total"] = int(e.sum())
+        return {"ended": ended, "held": h.value, "lost": lo.value, "idle": i.value}
+
+    def episodes_read(self, allow_lost: bool = False) -> dict:
+        """The outcome records held, sorted by (end tick, slot): slot, episode, record, reason (layout.EP_REASONS),
+        start_tick, end_tick, steps, iter_sum, iter_max, full_steps (steps at max_iter + 1 passes), stall_run (int
+        arrays), min_env_dist, xl, vl (K, 3): the state the episode's last control step saw.  Raises DatError where
+        records were lost to the table's capacity, unless allow_lost."""
+        c = self.episodes_counts()
+        if c["lost"] > 0 and not allow_lost:
+            raise L.DatError(f"episodes_read: {c['lost']} outcome records were lost to the table's capacity "
+                             f"({c['held']} held): open the episodes with a larger capacity or read and clear more often")
+        K = c["held"]
+        names = ("slot", "episode", "record", "reason", "steps", "iter_sum", "iter_max", "full_steps", "stall_run")
+        o = {k: np.zeros(K, dtype=np.int32) for k in names}
+        o.update(start_tick=np.zeros(K, dtype=np.int64), end_tick=np.zeros(K, dtype=np.int64),
+                 min_env_dist=np.zeros(K), xl=np.zeros((K, 3)), vl=np.zeros((K, 3)))
+        L.check(self._lib.dat_episode_read(
+            self._h, 0, K, L.ptr(o["slot"], L.I), L.ptr(o["episode"], L.I), L.ptr(o["record"], L.I),
+            L.ptr(o["reason"], L.I), L.ptr(o["start_tick"], L.LL), L.ptr(o["end_tick"], L.LL), L.ptr(o["steps"], L.I),
+            L.ptr(o["iter_sum"], L.I), L.ptr(o["iter_max"], L.I), L.ptr(o["full_steps"], L.I),
+            L.ptr(o["stall_run"], L.I), L.ptr(o["min_env_dist"]), L.ptr(o["xl"]), L.ptr(o["vl"])))
+        order = np.lexsort((o["slot"], o["end_tick"]))
+        return {k: v[order] for k, v in o.items()}
+
+    def episodes_clear(self) -> None:
+        """Empty the outcome table and zero `lost`; totals, idle slots and the running episodes stay."""
+        L.check(self._lib.dat_episode_clear(self._h))
+
+    def episodes_end(self) -> None:
+        """Close the episodes: closed_loop is the plain loop again (the scenarios stay as they are)."""
+        L.check(self._lib.dat_episode_end(self._h))
+
+    def episodes_slots(self) -> dict:
+        """Per slot: record (the pool record its running episode started from), episodes (finished), steps (control
+        steps of the running episode), idle."""
+        o = {k: np.zeros(self.batch, dtype=np.int32) for k in ("record", "episodes", "steps", "idle")}
+        L.check(self._lib.dat_episode_slots(self._h, L.ptr(o["record"], L.I), L.ptr(o["episodes"], L.I),
+                                            L.ptr(o["steps"], L.I), L.ptr(o["idle"], L.I)))
+        o["idle"] = o["idle"].astype(bool)
+        return o
+
+    def episodes_respawns(self) -> Tuple[int, int, int]:
+        """(respawns by the early pass: 0 by construction, respawns by every other pass, ending scenarios the early
+        gate left to the rest pass) since episodes_begin -- dat_get_episode_respawns."""
+        e, r, d = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(self._lib.dat_get_episode_respawns(self._h, ctypes.byref(e), ctypes.byref(r), ctypes.byref(d)))
+        return e.value, r.value, d.value
+
     # -- the closed loop's log (dat_log_*): closed_loop records into HBM, log_read copies the records out
     def log_begin(self, scenarios=None, log_every: Optional[int] = None, hl_capacity: int = 100,
                   summary: bool = False) -> None:

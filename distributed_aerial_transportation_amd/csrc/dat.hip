@@ -1,5 +1,6 @@
 // dat.hip -- the host side of libdat.so: the handle, the per-scenario array lists, the side streams, the step chain
-// and the closed loop's schedules, the log, the checkpoints, and every dat_* export of the C-ABI (include/dat.h).
+// and the closed loop's schedules, the log, the checkpoints, the episodes, and every dat_* export of the C-ABI
+// (include/dat.h).
 // No kernel lives here: the gfx950 kernels are the units beside it (dat_launch.hpp lists them, dat_cent.hip the
 // centralized one), reached through their launchers, and this file says in what order, on which stream and between
 // which events they run.
@@ -36,6 +37,7 @@
 #include "../../include/dat.h"
 #include "dat_cadmm_lds.hpp"
 #include "dat_ckpt.hpp"
+#include "dat_episode_host.hpp"
 #include "dat_kargs.hpp"
 #include "dat_launch.hpp"
 
@@ -58,10 +60,11 @@ int fail(const std::string& m) {
 
 // lg: the open log's arguments at this launch (dat_closed_loop), or null: the plain kernel
 // adv: the pass of the closed loop's advance overlap (ADV_ALL: every scenario)
+// ep: the open episodes' arguments at this launch (dat_closed_loop), or null
 hipError_t launch_rollout(const KArgs& a, int B, hipStream_t stream, int steps, double dt, const double* fdes,
-                          const LogArgs* lg = nullptr, int adv = ADV_ALL) {
+                          const LogArgs* lg = nullptr, int adv = ADV_ALL, const EpArgs* ep = nullptr) {
   const int G = 64 / a.n;
-  return launch_k_rollout_agents(lg, adv, (B + G - 1) / G, stream, a, steps, dt, fdes);
+  return launch_k_rollout_agents(lg, adv, (B + G - 1) / G, stream, a, steps, dt, fdes, ep);
 }
 
 }  // namespace
@@ -103,8 +106,22 @@ struct side_stream {
   hipStream_t st = nullptr;
   hipEvent_t ev[3] = {};
 };
+// The open episodes (dat_episode_begin .. dat_episode_end): the rules, the pool's records and the outcome table in
+// HBM, and the counters the kernels append through (EpCounter).  The accumulators are an array of the handle's
+// table (epacc), allocated with the others.
+struct dat_episodes {
+  bool open = false;
+  dat_episode_rules rules = {};
+  double* pool = nullptr;
+  int P = 0;
+  double* table = nullptr;
+  int cap = 0;
+  unsigned long long* cnt = nullptr;
+};
 struct dat_handle {
   dat_log log;
+  dat_episodes ep;
+  EpAcc* epacc = nullptr;
   dat_config cfg;
   int P = 0, S = 0;
   hipStream_t stream = nullptr;
@@ -204,7 +221,7 @@ struct dat_handle {
 // these lists and from nothing else: a new array is one line here plus its two members.  Beyond the lists only
 // the kernel that indexes an array knows its stride.  (counter and iters: the ints of a checkpoint record,
 // DAT_CK_INT_FIELDS, which states no extent.  erows: SoA over the scenarios of a sub-batch, KArgs::erows.)
-#define DAT_ARRAYS_ALL(X, n) X(counter, 1) X(iters, 1) X(acc, 6) X(qstatus, n) X(mind, 1) X(col, 1)
+#define DAT_ARRAYS_ALL(X, n) X(counter, 1) X(iters, 1) X(acc, 6) X(qstatus, n) X(mind, 1) X(col, 1) X(epacc, 1)
 #define DAT_ARRAYS_CADMM(X, n)                                                              \
   X(need, 1) X(ipmx, 1) X(slist, 1) X(rlist, 1) X(done, 1) X(adv, 1) X(rres, RRES_INTS)     \
   X(erows, 4 * DAT_NENV * (n)) X(emask, n) X(wrec, (n) * WREC_SIZE) X(best, (n) * BEST_REC)
@@ -484,6 +501,33 @@ int log_admit(const dat_handle* h, int hl_steps) {
   return 0;
 }
 
+// the open episodes' kernel arguments for the sub-batch of scenarios [off, ...) at the step of tick `tick`
+dat::CkArgs ck_args(const dat_handle* h);  // (below, with the checkpoints)
+EpArgs ep_args(const dat_handle* h, int off, long long tick) {
+  const dat_episodes& e = h->ep;
+  EpArgs a;
+  a.rules = e.rules;
+  a.pool = e.pool;
+  a.P = e.P;
+  a.batch = h->cfg.batch;
+  a.off = off;
+  a.hl_every = h->cfg.hl_every;
+  a.tick = tick;
+  a.table = e.table;
+  a.cap = e.cap;
+  a.cnt = e.cnt;
+  a.ck = ck_args(h);
+  return a;
+}
+
+void ep_free(dat_handle* h) {
+  dat_episodes& e = h->ep;
+  dfree(h, e.pool);
+  dfree(h, e.table);
+  dfree(h, e.cnt);
+  e = dat_episodes();
+}
+
 // ---- the step chain ------------------------------------------------------------------------------------------
 // A control step is desired acceleration -> env rows and class keys -> class sort -> drain, and in the closed loop
 // the rollout; each piece is stated once below, for one sub-batch.  dat_control_step, dat_control_steps and
@@ -583,10 +627,12 @@ int launch_step(const dat_handle* h, const Sub& u, bool timed = true) {
 
 // The rollout of a closed-loop step in the pass `mode`; with a log open the recording kernel, at the log's clock
 // (sub-batch streams run unsynchronised: the record index is the sub-batch's own step count).
+// With episodes open the kernel with the episode flag, at the step's tick (u.a.tick).
 hipError_t launch_step_rollout(const dat_handle* h, const Sub& u, int mode = ADV_ALL) {
   const LogArgs lg = h->log.open ? log_args(h, u.off) : LogArgs();
+  const EpArgs ep = h->ep.open ? ep_args(h, u.off, u.a.tick) : EpArgs();
   return launch_rollout(u.a, u.a.B, u.st, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes,
-                        h->log.open ? &lg : nullptr, mode);
+                        h->log.open ? &lg : nullptr, mode, h->ep.open ? &ep : nullptr);
 }
 
 // A pass (ADV_EARLY / ADV_REST) of the overlap and the pipeline: the rollout of the step and, with `inputs`, the next
@@ -603,8 +649,9 @@ int launch_advance(const dat_handle* h, const Sub& u, int mode, bool inputs) {
   nx.a.tick = u.a.tick + h->cfg.hl_every;
   if (inputs && mode != ADV_ALL && fused_ready(h)) {
     const int G = 64 / u.a.n;
+    const EpArgs ep = h->ep.open ? ep_args(h, u.off, u.a.tick) : EpArgs();
     HIPCHK(launch_k_advance(mode, (u.a.B + G - 1) / G, u.st, nx.a, h->cfg.hl_every, h->cfg.dt, (const double*)u.a.fdes,
-                            (double*)u.a.acc, u.kc_lo, u.kc_hi));
+                            (double*)u.a.acc, u.kc_lo, u.kc_hi, h->ep.open ? &ep : nullptr));
     ++h->n_advance;
     return 0;
   }
@@ -1068,6 +1115,7 @@ int dat_destroy(dat_handle* h) {
   for (void* p : h->allocs)
     if (p) (void)hipFree(p);
   log_free(h);
+  h->ep = dat_episodes();  // (its buffers went with the list)
   if (h->qempty) (void)hipHostFree(h->qempty);
   for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
   for (hipStream_t s : h->streams) (void)hipStreamDestroy(s);
@@ -1235,6 +1283,9 @@ int dat_checkpoint_save(dat_handle* h, const int* scenarios, int count, void* bl
 int dat_checkpoint_load(dat_handle* h, const void* blob, long long bytes, const int* records, const int* scenarios,
                         int count) {
   if (!h) return fail("dat_checkpoint_load: null handle");
+  if (h->ep.open)
+    return fail("dat_checkpoint_load: episodes are open on the handle (a loaded scenario would not be the episode its "
+                "slot is recorded to run): dat_episode_end first; nothing was written");
   std::string m;
   long long lo = 0, hi = 0;
   if (ck_check_load(h->cfg.mode, h->cfg.n, h->cfg.batch, blob, bytes, records, scenarios, count, &lo, &hi, &m))
@@ -1355,6 +1406,9 @@ int dat_rollout(dat_handle* h, int steps, const double* f_des) {
 // Every launch that computes a desired acceleration carries the tick it is evaluated at (KArgs::tick; the tracking law,
 // dat_set_tracking): step k's is clock + k hl_every, and the passes that compute step k + 1's inputs carry that
 // step's (launch_advance).  The call advances the clock by hl_steps x hl_every.
+// With episodes open (dat_episode_begin) every pass that rolls scenarios out launches the kernel with the episode flag
+// (launch_step_rollout, launch_advance): a scenario's episode step stands between the pass's gate and its rollout, the
+// early pass leaves an ending scenario to the rest pass, and the schedules stay what they are.
 // With the rigid-payload plant (dat_set_plant, centralized handles) a step is k_cent and k_rp_advance, which runs the
 // payload's hl_every steps and the next step's desired acceleration, on the serial schedule.
 // What the early pass may touch while the drain runs: a finished scenario's state, acc, env rows / mask, sort key
@@ -1447,6 +1501,9 @@ int dat_closed_loop(dat_handle* h, int hl_steps) {
 // ---- the tracking law, the clock and the plant ------------------------------------------------------------------
 int dat_set_tracking(dat_handle* h, const double* rec, int per_scenario) {
   if (!h) return fail("dat_set_tracking: null handle");
+  if (rec && h->ep.open)
+    return fail("dat_set_tracking: episodes do not run under tracking records yet: dat_episode_end first; the law in "
+                "force is unchanged");
   const size_t count = per_scenario ? (size_t)h->cfg.batch : 1;
   if (rec) {  // checked on the host before anything is copied or launched
     static const char* const names[DAT_TRACK_SIZE] = {"CX", "CY", "RADIUS", "HEIGHT", "FREQ", "T0", "KP", "KV",
@@ -1493,6 +1550,8 @@ int dat_set_plant(dat_handle* h, int plant) {
     return fail("dat_set_plant: the rigid-payload plant (DAT_PLANT_RP) runs on centralized handles only");
   if (plant == DAT_PLANT_RP && h->log.open)
     return fail("dat_set_plant: the log does not record the rigid-payload plant (DAT_PLANT_RP) yet: close the log");
+  if (plant == DAT_PLANT_RP && h->ep.open)
+    return fail("dat_set_plant: episodes do not run on the rigid-payload plant (DAT_PLANT_RP) yet: dat_episode_end first");
   h->plant = plant;
   return 0;
 }
@@ -1952,6 +2011,7 @@ int dat_pmrl_forward(dat_handle* h, const double* f, double* ddq, double* dvl, d
 int dat_log_begin(dat_handle* h, const int* scenarios, int count, int log_every, int hl_capacity, int summary) {
   if (!h) return fail("null handle");
   if (h->log.open) return fail("dat_log_begin: a log is already open (dat_log_end first)");
+  if (h->ep.open) return fail("dat_log_begin: the log does not record episodes yet: dat_episode_end first");
   if (h->plant == DAT_PLANT_RP)
     return fail("dat_log_begin: the log does not record the rigid-payload plant (DAT_PLANT_RP) yet");
   const int B = h->cfg.batch, n = h->cfg.n;
@@ -2103,6 +2163,159 @@ int dat_log_end(dat_handle* h) {
   HIPCHK(hipStreamSynchronize(h->stream));
   log_free(h);
   return 0;
+}
+
+// ---- episodes --------------------------------------------------------------------------------------------------
+void dat_episode_default_rules(dat_episode_rules* r) {
+  if (!r) return;
+  memset(r, 0, sizeof(*r));
+  r->goal_x = HUGE_VAL;
+  r->bound = HUGE_VAL;
+  r->wrap = 1;
+}
+
+int dat_episode_begin(dat_handle* h, const dat_episode_rules* rules, const void* pool_blob, long long bytes,
+                      int capacity) {
+  if (!h) return fail("dat_episode_begin: null handle");
+  if (h->ep.open) return fail("dat_episode_begin: episodes are already open (dat_episode_end first)");
+  if (h->log.open) return fail("dat_episode_begin: the log does not record episodes yet: dat_log_end first");
+  if (h->plant == DAT_PLANT_RP)
+    return fail("dat_episode_begin: episodes do not run on the rigid-payload plant (DAT_PLANT_RP) yet");
+  if (h->track) return fail("dat_episode_begin: episodes do not run under tracking records yet: dat_set_tracking(NULL) first");
+  std::string m;
+  int P = 0;
+  if (ep_check_begin(h->cfg.mode, h->cfg.n, rules, pool_blob, bytes, capacity, &P, &m)) return fail(m);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipStream_t s : h->streams) HIPCHK(hipStreamSynchronize(s));
+  const int B = h->cfg.batch;
+  const dat::CkArgs c = ck_args(h);
+  const size_t words = (size_t)P * c.words;
+  // slot s runs record s mod P first (its episode 0); without wrap a slot beyond the pool is idle from the start
+  std::vector<EpAcc> acc((size_t)B);
+  std::vector<int> recs((size_t)B);
+  unsigned long long cnt[EPC_WORDS] = {0};
+  for (int s = 0; s < B; ++s) {
+    int idle = 0;
+    recs[(size_t)s] = episode_record(s, 0, B, P, rules->wrap, &idle);
+    episode_start(acc[(size_t)s], recs[(size_t)s], h->clock, 0, idle);
+    cnt[EPC_IDLE] += idle ? 1 : 0;
+  }
+  dat_episodes& e = h->ep;
+  if (dalloc(h, &e.pool, words) || dalloc(h, &e.table, (size_t)std::max(capacity, 1) * DAT_EP_WORDS) ||
+      dalloc(h, &e.cnt, (size_t)EPC_WORDS) || ck_grow(h, &h->ck_list, &h->ck_list_cap, (size_t)B)) {
+    (void)hipGetLastError();
+    ep_free(h);
+    return -1;
+  }
+  const hipStream_t st = h->stream;
+  hipError_t r = hipMemcpyAsync(e.pool, (const char*)pool_blob + DAT_CK_HEADER_BYTES, sizeof(double) * words,
+                                hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(e.cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(h->epacc, acc.data(), sizeof(EpAcc) * (size_t)B, hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(h->ck_list, recs.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, st);
+  if (r == hipSuccess)
+    r = launch_k_ckpt_scatter(ck_wide(c), st, c, (const double*)e.pool, (const int*)h->ck_list, nullptr, 0, B);
+  if (r == hipSuccess) r = hipStreamSynchronize(st);
+  if (r != hipSuccess) {
+    ep_free(h);
+    return fail(std::string("dat_episode_begin: ") + hipGetErrorString(r));
+  }
+  e.rules = *rules;
+  e.P = P;
+  e.cap = capacity;
+  e.open = true;
+  return 0;
+}
+
+int dat_episode_counts(dat_handle* h, long long* ended, long long* held, long long* lost, long long* idle) {
+  if (!h) return fail("dat_episode_counts: null handle");
+  if (!h->ep.open) return fail("dat_episode_counts: no episodes open");
+  unsigned long long c[EPC_WORDS];
+  if (read_words(h, h->ep.cnt, c, EPC_WORDS)) return -1;
+  if (ended)
+    for (int k = 0; k < DAT_EP_NREASON; ++k) ended[k] = (long long)c[EPC_ENDED + k];
+  if (held) *held = (long long)std::min<unsigned long long>(c[EPC_COUNT], (unsigned long long)h->ep.cap);
+  if (lost) *lost = (long long)c[EPC_LOST];
+  if (idle) *idle = (long long)c[EPC_IDLE];
+  return 0;
+}
+
+int dat_episode_read(dat_handle* h, int first, int count, int* slot, int* episode, int* record, int* reason,
+                     long long* start_tick, long long* end_tick, int* steps, int* iter_sum, int* iter_max,
+                     int* full_steps, int* stall_run, double* min_env_dist, double* xl, double* vl) {
+  if (!h) return fail("dat_episode_read: null handle");
+  if (!h->ep.open) return fail("dat_episode_read: no episodes open");
+  long long held = 0;
+  if (dat_episode_counts(h, nullptr, &held, nullptr, nullptr)) return -1;
+  std::string m;
+  if (ep_check_read(first, count, held, &m)) return fail(m);
+  if (count == 0) return 0;
+  std::vector<double> w((size_t)count * DAT_EP_WORDS);
+  HIPCHK(hipMemcpyAsync(w.data(), h->ep.table + (size_t)first * DAT_EP_WORDS, sizeof(double) * w.size(),
+                        hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (size_t k = 0; k < (size_t)count; ++k) {
+    const double* r = w.data() + k * DAT_EP_WORDS;
+    const auto ints = [&](int word, int* lo, int* hi) {
+      int v[2];
+      memcpy(v, r + word, sizeof(v));
+      if (lo) lo[k] = v[0];
+      if (hi) hi[k] = v[1];
+    };
+    ints(DAT_EP_SLOT, slot, episode);
+    ints(DAT_EP_RECORD, record, reason);
+    ints(DAT_EP_STEPS, steps, iter_sum);
+    ints(DAT_EP_ITMAX, iter_max, full_steps);
+    ints(DAT_EP_RUN, stall_run, nullptr);
+    if (start_tick) memcpy(start_tick + k, r + DAT_EP_START, 8);
+    if (end_tick) memcpy(end_tick + k, r + DAT_EP_END, 8);
+    if (min_env_dist) min_env_dist[k] = r[DAT_EP_MIND];
+    if (xl) memcpy(xl + 3 * k, r + DAT_EP_XL, sizeof(double) * 3);
+    if (vl) memcpy(vl + 3 * k, r + DAT_EP_VL, sizeof(double) * 3);
+  }
+  return 0;
+}
+
+int dat_episode_clear(dat_handle* h) {
+  if (!h) return fail("dat_episode_clear: null handle");
+  if (!h->ep.open) return fail("dat_episode_clear: no episodes open");
+  static_assert(EPC_COUNT == 0 && EPC_LOST == 1, "the cursor and the lost count are cleared together");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipMemsetAsync(h->ep.cnt, 0, 2 * sizeof(unsigned long long), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dat_episode_end(dat_handle* h) {
+  if (!h) return fail("dat_episode_end: null handle");
+  if (!h->ep.open) return fail("dat_episode_end: no episodes open");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipStream_t s : h->streams) HIPCHK(hipStreamSynchronize(s));
+  ep_free(h);
+  return 0;
+}
+
+int dat_episode_slots(dat_handle* h, int* record, int* episodes, int* steps, int* idle) {
+  if (!h) return fail("dat_episode_slots: null handle");
+  if (!h->ep.open) return fail("dat_episode_slots: no episodes open");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  std::vector<EpAcc> acc((size_t)h->cfg.batch);
+  HIPCHK(hipMemcpyAsync(acc.data(), h->epacc, sizeof(EpAcc) * acc.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (size_t s = 0; s < acc.size(); ++s) {
+    if (record) record[s] = acc[s].record;
+    if (episodes) episodes[s] = acc[s].episodes;
+    if (steps) steps[s] = acc[s].steps;
+    if (idle) idle[s] = acc[s].idle;
+  }
+  return 0;
+}
+
+int dat_get_episode_respawns(dat_handle* h, long long* early, long long* rest, long long* deferred) {
+  if (!h) return fail("dat_get_episode_respawns: null handle");
+  if (!h->ep.open) return fail("dat_get_episode_respawns: no episodes open");
+  static_assert(EPC_DEFERRED == EPC_RESPAWN + 2, "the three words are read together");
+  return read_words(h, h->ep.cnt + EPC_RESPAWN, {early, rest, deferred});
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // dat_k_step.hip -- the kernels of a step around the drains: the rollout / advance family (k_env_class<*>, k_bucket,
-// k_bucket_adv<*>, k_bucket_scatter<*>, k_rollout_agents<*, *>, k_desired<*>, k_advance<*>, k_low_level), and with
+// k_bucket_adv<*>, k_bucket_scatter<*>, k_rollout_agents<*, *, *>, k_desired<*>, k_advance<*, *>, k_low_level), and with
 // them k_warm, k_env, the rigid-payload, PMRL and checkpoint kernels.  The family is one unit: its kernels share
 // device functions (ll_control_agent, rollout_lanes, env_class_lanes) for which the inliner's choices depend on the
 // callers the unit holds (the comment at k_low_level), so a kernel compiled without its siblings comes out different.
@@ -373,30 +373,140 @@ __device__ inline void mountain_of(const KArgs& a, int sc, double* m) {
     for (int k = 0; k < DAT_MOUNTAIN_SIZE; ++k) m[k] = a.mountain[(size_t)f * DAT_MOUNTAIN_SIZE + k];
   }
 }
+// ---- episodes (dat_episode_*; the rule: dat_episode.hpp) -------------------------------------------------------------
+// the array and the word in it behind word x of scenario s's checkpoint record (null: an int word or padding)
+__device__ __forceinline__ double* ep_word(const dat::CkArgs& c, int s, int x) {
+  for (int k = 0; k < c.nf; ++k) {
+    const int d = x - c.off[k];
+    if ((unsigned)d < (unsigned)c.w[k]) return c.f[k] + (size_t)s * c.w[k] + d;
+  }
+  return nullptr;
+}
+// The episode step of the scenarios of one block, between their control step and their rollout, for the lanes that
+// take part in the pass (valid; lane ls * n + i: agent i of scenario sc of the launch, off + sc of the batch).  The
+// scenario's first lane updates a copy of the accumulators and evaluates the rule on the state in memory and the
+// step's published outputs; the verdict goes to the scenario's lanes.
+//   The episode goes on: the accumulators are stored, the pass rolls the scenario out.
+//   It ends, ADV_EARLY: nothing is stored and the scenario leaves the pass (*valid = false): unmarked, it is the rest
+//     pass's, which runs after every drain of the step has ended and comes to the same verdict from the same inputs.
+//     (The drain that finished the scenario stores its warm state with plain stores and may still be running on
+//     other CUs: a respawn here would race with lines not yet written back.  DESIGN.md 3.)
+//   It ends, otherwise: the first lane appends the outcome and starts the accumulators of the slot's next episode;
+//     the scenario's lanes copy the pool record over the scenario's arrays, each word to the place k_ckpt_scatter
+//     gives it.  done[] and adv[] stay as the pass leaves them for a scenario it advanced.  Returns true: the pass does
+//     not roll the scenario out (its next inputs come from the new state, like any scenario's of the pass).
+// An idle slot (wrap = 0, the pool used up) is rolled out like a scenario of the plain loop.
+// Every lane of the wavefront must call it (shuffles inside).
+template <int ADV>
+__device__ __forceinline__ bool episode_lanes(const KArgs& a, const EpArgs& ep, int n, int ls, int i, int sc,
+                                              bool* valid) {
+  int reason = DAT_EP_NONE;
+  if (*valid && i == 0) {
+    EpAcc c = a.epacc[sc];
+    if (!c.idle) {
+      const double* st = a.state + (size_t)sc * a.S;
+      double xl[3], vl[3];
+      for (int k = 0; k < 3; ++k) {
+        xl[k] = st[DAT_S_XL(n) + k];
+        vl[k] = st[DAT_S_VL(n) + k];
+      }
+      // (beside the running drain iters comes as the drain published it: write-through, read past the caches;
+      // col and mind were written ahead of the drain)
+      const int it = ADV == ADV_EARLY ? ld_wt(a.iters + sc) : a.iters[sc];
+      reason = episode_step(ep.rules, a.max_iter, xl, vl, it, a.col[sc], a.mind[sc], c);
+      if (reason == DAT_EP_NONE) {
+        a.epacc[sc] = c;
+      } else if (ADV == ADV_EARLY) {
+        atomicAdd(ep.cnt + EPC_DEFERRED, 1ull);
+      } else {
+        const int s = ep.off + sc;
+        atomicAdd(ep.cnt + EPC_ENDED + reason, 1ull);
+        atomicAdd(ep.cnt + EPC_RESPAWN + 1, 1ull);
+        const unsigned long long at = atomicAdd(ep.cnt + EPC_COUNT, 1ull);
+        if (at < (unsigned long long)ep.cap) {
+          double* r = ep.table + (size_t)at * DAT_EP_WORDS;
+          r[DAT_EP_SLOT] = __hiloint2double(c.episodes, s);
+          r[DAT_EP_RECORD] = __hiloint2double(reason, c.record);
+          r[DAT_EP_START] = __longlong_as_double(c.start);
+          r[DAT_EP_END] = __longlong_as_double(ep.tick);
+          r[DAT_EP_STEPS] = __hiloint2double(c.isum, c.steps);
+          r[DAT_EP_ITMAX] = __hiloint2double(c.full, c.imax);
+          r[DAT_EP_RUN] = __hiloint2double(0, c.run);
+          r[DAT_EP_MIND] = c.mind;
+          for (int k = 0; k < 3; ++k) {
+            r[DAT_EP_XL + k] = xl[k];
+            r[DAT_EP_VL + k] = vl[k];
+          }
+        } else {
+          atomicAdd(ep.cnt + EPC_LOST, 1ull);
+        }
+        int idle;
+        const int rec = episode_record(s, c.episodes + 1, ep.batch, ep.P, ep.rules.wrap, &idle);
+        if (idle) atomicAdd(ep.cnt + EPC_IDLE, 1ull);
+        EpAcc nx;
+        episode_start(nx, rec, ep.tick + ep.hl_every, c.episodes + 1, idle);
+        a.epacc[sc] = nx;
+        reason = -1 - rec;  // to the scenario's lanes: respawn from record rec
+      }
+    }
+  }
+  reason = __shfl(reason, (ls * n) & 63);
+  if (!*valid || reason == DAT_EP_NONE) return false;
+  if constexpr (ADV == ADV_EARLY) {
+    *valid = false;
+    return false;
+  } else {
+    const dat::CkArgs& c = ep.ck;
+    const int s = ep.off + sc;
+    const double* rec = ep.pool + (size_t)(-1 - reason) * c.words;
+    for (int x = i; x < c.words; x += n) {
+      const double v = rec[x];
+      if ((unsigned)(x - c.ints_off) < (unsigned)CK_INT_WORDS) {
+        const int i0 = 2 * (x - c.ints_off);
+        if (c.ints[i0]) c.ints[i0][s] = __double2loint(v);
+        if (c.ints[i0 + 1]) c.ints[i0 + 1][s] = __double2hiint(v);
+      } else if (double* p = ep_word(c, s, x)) {
+        *p = v;
+      }
+    }
+    return true;
+  }
+}
+
 // ADV (dat_kargs.hpp): the scenarios that take part.  The early pass runs beside the drain on the scenarios whose
 // done stamp is this step's and reads their f_des as the drain published it (write-through, past the caches); it
 // marks them in adv, and both passes count their scenarios (advcnt).  ADV_ALL compiles to the kernel without a gate.
+// EP: episodes are open (dat_episode_begin): a scenario's episode step stands between the gate and the rollout
+// (episode_lanes); a respawned scenario takes part in the pass and is not rolled out.  EP = false compiles to the
+// kernel without any of it.
 // The body of k_rollout_agents for the lanes of one block, stated once for k_rollout_agents and k_advance: the gate
 // and its count, the steps, the write-back and the adv[] mark.  xs: 64 x RO_X doubles of LDS.  Returns false when no
 // scenario of the block takes part (nothing was done: the kernel returns); *took_part: this lane's scenario took part.
-template <bool LOG, int ADV>
+template <bool LOG, int ADV, bool EP = false>
 __device__ __forceinline__ bool rollout_lanes(const KArgs& a, int steps, double dt, const double* fdes,
                                               const std::conditional_t<LOG, LogArgs, NoLog>& lg, double* xs,
-                                              bool* took_part) {
+                                              bool* took_part, const std::conditional_t<EP, EpArgs, NoEp>& ep = {}) {
   static_assert(!LOG || ADV == ADV_ALL, "the logging rollout is not gated");
+  static_assert(!LOG || !EP, "the logging rollout knows no episodes");
   const int n = a.n, G = 64 / n, NT = G * n;
   const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
   const int sc = blockIdx.x * G + ls;
   bool valid = lane < NT && sc < a.B;
+  [[maybe_unused]] bool roll = true;  // EP: false where the scenario was respawned instead
   if constexpr (ADV != ADV_ALL) {
     // (a scenario's lanes follow its first lane's reading of the stamp)
     valid = __shfl((int)(valid && adv_gate<ADV, true>(a, sc)), (ls * n) & 63) != 0 && valid;
     // (the stamp is read before the bytes it covers: the loads below are issued after this branch)
     asm volatile("" ::: "memory");
+    if constexpr (EP) roll = !episode_lanes<ADV>(a, ep, n, ls, i, sc, &valid);
     const unsigned long long took = __ballot(valid && i == 0);
     if (!took) return false;  // no scenario of the block takes part (one wavefront: uniform)
     if (lane == 0) atomicAdd(a.advcnt + (ADV == ADV_EARLY ? 0 : 1), (unsigned long long)__builtin_popcountll(took));
+  } else if constexpr (EP) {
+    roll = !episode_lanes<ADV>(a, ep, n, ls, i, sc, &valid);
   }
+  *took_part = valid;
+  if constexpr (EP) valid = valid && roll;  // from here on: the scenarios the pass rolls out
   const double* prm = valid ? prm_of(a, sc) : a.params;
   double* g = valid ? a.state + (size_t)sc * a.S : nullptr;
   double R[9], W[3], xl[3], vl[3], Rl[9], wl[3], fd[3];
@@ -535,15 +645,15 @@ __device__ __forceinline__ bool rollout_lanes(const KArgs& a, int steps, double 
       if constexpr (ADV == ADV_EARLY) a.adv[sc] = a.serial;
     }
   }
-  *took_part = valid;
   return true;
 }
-template <bool LOG, int ADV>
+template <bool LOG, int ADV, bool EP = false>
 __global__ __launch_bounds__(64) void k_rollout_agents(KArgs a, int steps, double dt, const double* fdes,
-                                                       std::conditional_t<LOG, LogArgs, NoLog> lg) {
+                                                       std::conditional_t<LOG, LogArgs, NoLog> lg,
+                                                       std::conditional_t<EP, EpArgs, NoEp> ep) {
   __shared__ double xs[64 * RO_X];
   bool took;
-  (void)rollout_lanes<LOG, ADV>(a, steps, dt, fdes, lg, xs, &took);
+  (void)rollout_lanes<LOG, ADV, EP>(a, steps, dt, fdes, lg, xs, &took, ep);
 }
 
 // RQPLowLevelController.control (control/rqp_centralized.py:518-535) at the current states: thrust
@@ -784,11 +894,11 @@ __global__ void k_desired(KArgs a, double* acc) {
 // before its reads: k_desired's by the scenario's first lane, the env rows' by every lane, from memory as in the
 // separate kernels.  One grid waits once for the SIMDs the drain's wavefronts free, and the state is not fetched
 // from memory again.  Registers: bound as k_env_class (256); the rollout's are dead at the barrier.
-template <int ADV>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_advance(KArgs a, int steps, double dt,
-                                                                                        const double* fdes,
-                                                                                        double* acc, int* kc_lo,
-                                                                                        int* kc_hi) {
+// EP: with episodes open (rollout_lanes): a scenario respawned instead of rolled out gets its next inputs from the new state.
+template <int ADV, bool EP = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_advance(
+    KArgs a, int steps, double dt, const double* fdes, double* acc, int* kc_lo, int* kc_hi,
+    std::conditional_t<EP, EpArgs, NoEp> ep) {
   static_assert(ADV == ADV_EARLY || ADV == ADV_REST, "the ungated step runs the three kernels");
   __shared__ double xs[64 * RO_X];
   __shared__ int nd[64], cl[64];
@@ -798,7 +908,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
   const int lane = threadIdx.x, ls = lane / n, i = lane - ls * n;
   const int sc = blockIdx.x * G + ls;
   bool valid;
-  if (!rollout_lanes<false, ADV>(a, steps, dt, fdes, NoLog{}, xs, &valid)) return;
+  if (!rollout_lanes<false, ADV, EP>(a, steps, dt, fdes, NoLog{}, xs, &valid, ep)) return;
   __syncthreads();  // the state is stored before it is read back
   if (valid && i == 0) desired_of(a, sc, acc);
   double lhs[DAT_NENV][3], rhs[DAT_NENV];
@@ -992,22 +1102,35 @@ hipError_t launch_k_bucket_scatter(int adv, hipStream_t st, int B, const int* ne
   return hipGetLastError();
 }
 hipError_t launch_k_rollout_agents(const LogArgs* lg, int adv, int blocks, hipStream_t st, const KArgs& a, int steps,
-                                   double dt, const double* fdes) {
+                                   double dt, const double* fdes, const EpArgs* ep) {
   constexpr auto k_log = k_rollout_agents<true, ADV_ALL>;
   constexpr auto k_all = k_rollout_agents<false, ADV_ALL>;
   constexpr auto k_early = k_rollout_agents<false, ADV_EARLY>;
   constexpr auto k_rest = k_rollout_agents<false, ADV_REST>;
+  constexpr auto e_all = k_rollout_agents<false, ADV_ALL, true>;
+  constexpr auto e_early = k_rollout_agents<false, ADV_EARLY, true>;
+  constexpr auto e_rest = k_rollout_agents<false, ADV_REST, true>;
+  if (lg && ep) return hipErrorInvalidValue;  // (dat_episode_begin and dat_log_begin exclude each other)
   if (lg)
-    hipLaunchKernelGGL(k_log, dim3(blocks), dim3(64), 0, st, a, steps, dt, fdes, *lg);
+    hipLaunchKernelGGL(k_log, dim3(blocks), dim3(64), 0, st, a, steps, dt, fdes, *lg, NoEp{});
+  else if (ep)
+    hipLaunchKernelGGL(adv == ADV_EARLY ? e_early : adv == ADV_REST ? e_rest : e_all, dim3(blocks), dim3(64), 0, st, a,
+                       steps, dt, fdes, NoLog{}, *ep);
   else
     hipLaunchKernelGGL(adv == ADV_EARLY ? k_early : adv == ADV_REST ? k_rest : k_all, dim3(blocks), dim3(64), 0, st, a,
-                       steps, dt, fdes, NoLog{});
+                       steps, dt, fdes, NoLog{}, NoEp{});
   return hipGetLastError();
 }
 hipError_t launch_k_advance(int adv, int blocks, hipStream_t st, const KArgs& a, int steps, double dt,
-                            const double* fdes, double* acc, int* kc_lo, int* kc_hi) {
-  hipLaunchKernelGGL(adv == ADV_EARLY ? k_advance<ADV_EARLY> : k_advance<ADV_REST>, dim3(blocks), dim3(64), 0, st, a,
-                     steps, dt, fdes, acc, kc_lo, kc_hi);
+                            const double* fdes, double* acc, int* kc_lo, int* kc_hi, const EpArgs* ep) {
+  constexpr auto e_early = k_advance<ADV_EARLY, true>;
+  constexpr auto e_rest = k_advance<ADV_REST, true>;
+  if (ep)
+    hipLaunchKernelGGL(adv == ADV_EARLY ? e_early : e_rest, dim3(blocks), dim3(64), 0, st, a, steps, dt, fdes, acc,
+                       kc_lo, kc_hi, *ep);
+  else
+    hipLaunchKernelGGL(adv == ADV_EARLY ? k_advance<ADV_EARLY> : k_advance<ADV_REST>, dim3(blocks), dim3(64), 0, st, a,
+                       steps, dt, fdes, acc, kc_lo, kc_hi, NoEp{});
   return hipGetLastError();
 }
 hipError_t launch_k_low_level(hipStream_t st, const KArgs& a, const double* fdes, double* fo, double* Mo) {

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "dat_cadmm_step.hpp"
+#include "dat_episode.hpp"
 #include "dat_track.hpp"
 
 namespace dat {
@@ -139,6 +140,8 @@ struct KArgs {
                                  // rollout's x_ref / v_ref) is evaluated: t = tick dt.  An advance pass of step k
                                  // computes the inputs of step k + 1 and carries that step's tick.
   double dt;
+  EpAcc* epacc;                  // [B] the episodes' accumulators (dat_episode_*; read only by the kernels with the
+                                 // episode flag, which get the rest as EpArgs)
 };
 
 // Modes of the gated kernels (k_rollout_agents, k_desired, k_env_class): which scenarios of the grid take part

@@ -84,6 +84,32 @@ struct CkArgs {
   int *done, *adv;  // scatter: the closed loop's stamps of the scenarios written (null: the mode has none)
 };
 
+// The open episodes (dat_episode_*), handed to the kernels with the episode flag (k_rollout_agents<., ., true>,
+// k_advance<., true>) at every HL step: the rules, the pool, the outcome table and the record's segments in the
+// handle's arrays, which a respawn writes (ck: the whole batch's arrays, indexed by off + the sub-batch's scenario).
+enum EpCounter {
+  EPC_COUNT,                           // outcomes appended or dropped since the last clear: the table's cursor
+  EPC_LOST,                            // ... dropped, beyond the capacity
+  EPC_IDLE,                            // idle slots
+  EPC_ENDED,                           // [EPC_ENDED + reason] episodes ended per reason since dat_episode_begin
+  EPC_RESPAWN = EPC_ENDED + DAT_EP_NREASON,  // respawns by [0] the early pass (never), [1] every other pass;
+  EPC_DEFERRED = EPC_RESPAWN + 2,      // ending scenarios the early gate left to the rest pass
+  EPC_WORDS
+};
+struct EpArgs {
+  dat_episode_rules rules;
+  const double* pool;  // P records of ck.words words
+  int P;
+  int batch, off;      // the handle's batch; the global index of the launch's scenario 0 (sub-batches)
+  int hl_every;
+  long long tick;      // the tick of the control step the launch follows
+  double* table;       // cap outcome records of DAT_EP_WORDS words
+  int cap;
+  unsigned long long* cnt;  // EpCounter
+  CkArgs ck;
+};
+struct NoEp {};
+
 // ---- dat_k_cadmm.hip, dat_k_cadmm_adv.hip: forest ? k_cadmm<ADV> : k_cadmm0<ADV>, ADV the unit's; k_dd<false>, k_dd<true>
 hipError_t launch_k_cadmm(bool forest, int blocks, size_t lds, hipStream_t st, const KArgs& a);
 hipError_t launch_k_cadmm_adv(bool forest, int blocks, size_t lds, hipStream_t st, const KArgs& a);
@@ -107,11 +133,12 @@ hipError_t launch_k_bucket_adv(int adv, hipStream_t st, int B, const int* need, 
                                int serial);
 hipError_t launch_k_bucket_scatter(int adv, hipStream_t st, int B, const int* need, int* list, int* count,
                                    const int* advp, int serial, int* tab, int* other);
-// lg: the open log's arguments (k_rollout_agents<true, ADV_ALL>), or null
+// lg: the open log's arguments (k_rollout_agents<true, ADV_ALL>), or null; ep: the open episodes' (the instantiations
+// with the episode flag; not with a log), or null: the kernels as they are without episodes
 hipError_t launch_k_rollout_agents(const LogArgs* lg, int adv, int blocks, hipStream_t st, const KArgs& a, int steps,
-                                   double dt, const double* fdes);
+                                   double dt, const double* fdes, const EpArgs* ep = nullptr);
 hipError_t launch_k_advance(int adv, int blocks, hipStream_t st, const KArgs& a, int steps, double dt,
-                            const double* fdes, double* acc, int* kc_lo, int* kc_hi);
+                            const double* fdes, double* acc, int* kc_lo, int* kc_hi, const EpArgs* ep = nullptr);
 hipError_t launch_k_low_level(hipStream_t st, const KArgs& a, const double* fdes, double* fo, double* Mo);
 hipError_t launch_k_rp_rollout(hipStream_t st, const KArgs& a, int steps, double dt, const double* f);
 // acc: where the next step's desired acceleration goes (a.tick: that step's), or null: none

@@ -142,6 +142,28 @@
 #define DAT_CK_H_COUNT 24
 #define DAT_CK_H_PAD 32
 
+// ---- episodes (dat_episode_*; the rule: dat_episode.hpp) ----------------------------------------------------------
+// Reasons an episode ends for; the lowest code that fires wins, 0: the episode goes on.
+#define DAT_EP_NONE 0
+#define DAT_EP_DIVERGED 1
+#define DAT_EP_COLLISION 2
+#define DAT_EP_GOAL 3
+#define DAT_EP_STALL 4
+#define DAT_EP_TIME_LIMIT 5
+#define DAT_EP_NREASON 6
+// Outcome record, DAT_EP_WORDS 8-byte words; 32-bit ints packed two per word (the first in the low half).
+#define DAT_EP_SLOT 0         // ints: slot (the global scenario index), episode number of the slot
+#define DAT_EP_RECORD 1       // ints: pool record the episode started from, reason (DAT_EP_*)
+#define DAT_EP_START 2        // int64: tick of the episode's first control step, on the handle's clock
+#define DAT_EP_END 3          // int64: tick of its last control step
+#define DAT_EP_STEPS 4        // ints: control steps, sum of iters
+#define DAT_EP_ITMAX 5        // ints: maximum of iters, steps at max_iter + 1 passes
+#define DAT_EP_RUN 6          // ints: the stall run at the end, zero
+#define DAT_EP_MIND 7         // smallest min_env_dist of the episode's steps
+#define DAT_EP_XL 8           // terminal xl (3): the state the last control step saw
+#define DAT_EP_VL 11          // terminal vl (3)
+#define DAT_EP_WORDS 14
+
 #define DAT_BARK_RADIUS 0.3
 #define DAT_BARK_HALF_HEIGHT 2.0
 #define DAT_NENV 10            // env CBF rows per QP (control/rqp_cadmm.py:218)

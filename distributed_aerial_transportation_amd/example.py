@@ -263,5 +263,59 @@ def simulate(controller_type: str = "dual-decomposition", n: int = 3, T: float =
     return logs
 
 
+def monte_carlo(controller_type: str, n: int, starts: np.ndarray, forests: list, rules: dict, batch: int,
+                scenario_forest=None, chunk_hl: int = 50, max_hl: int = 100000, dt: float = 1e-3,
+                hl_rel_freq: int = 10, params: Optional[np.ndarray] = None, device: int = 0,
+                progress: bool = False) -> dict:
+    """A Monte Carlo campaign over the P initial conditions starts (P, 12n + 18) on `batch` slots of one GPU, on
+    the device-resident loop with episodes (BatchedController.episodes_begin): every start is flown once, from a
+    fresh controller, until a rule of `rules` (episodes_begin's keywords: goal_x, max_steps, stall_steps,
+    on_collision, bound) ends it; the slot then takes the next start.  forests[scenario_forest[s]] is the forest
+    of slot s (default: the first for every slot; [] for none).  The loop runs in calls of chunk_hl HL steps, the
+    outcome table read and cleared after each, until every slot is idle (at most max_hl HL steps: the rules must
+    end every episode, else RuntimeError).  Returns the outcome table of episodes_read, concatenated and sorted
+    by (end tick, slot), with "hl_steps" the HL steps run; record k of the table is starts[record[k]]."""
+    from .control import BatchedController
+
+    if controller_type not in CONTROLLER_TYPES:
+        raise NotImplementedError(controller_type)
+    starts = np.atleast_2d(np.asarray(starts, float))
+    P = starts.shape[0]
+    if "wrap" in rules:
+        raise ValueError("monte_carlo runs every start once: wrap is not a rule of the campaign")
+    prm = scenarios.params_block(n) if params is None else params
+    eng = BatchedController(controller_type, n, batch, prm, dt=dt, hl_every=hl_rel_freq, device=device)
+    try:
+        sf = np.zeros(batch, dtype=np.int32) if scenario_forest is None else np.asarray(scenario_forest, np.int32)
+        eng.set_forests(forests, sf if forests else None)
+        # the pool: P records with the constructor's warm state (the handle's, untouched so far) and the starts
+        pool = eng.checkpoint(np.zeros(P, dtype=np.int32))
+        arr = pool.arrays()
+        arr["state"][:] = starts
+        arr["counter"][:] = 0
+        eng.episodes_begin(pool, wrap=False, capacity=batch * chunk_hl, **rules)
+        parts, done = [], 0
+        while eng.episodes_counts()["idle"] < batch:
+            if done >= max_hl:
+                raise RuntimeError(f"monte_carlo: {max_hl} HL steps run and {eng.episodes_counts()['idle']} of "
+                                   f"{batch} slots idle: the rules do not end every episode")
+            eng.closed_loop(chunk_hl)
+            done += chunk_hl
+            parts.append(eng.episodes_read())
+            eng.episodes_clear()
+            if progress:
+                print(f"{done} HL steps: {eng.episodes_counts()}", flush=True)
+        eng.episodes_end()
+    finally:
+        eng.close()
+    keys = parts[0].keys() if parts else ()
+    out = {k: np.concatenate([p[k] for p in parts]) for k in keys}
+    if parts:
+        order = np.lexsort((out["slot"], out["end_tick"]))
+        out = {k: v[order] for k, v in out.items()}
+    out["hl_steps"] = done
+    return out
+
+
 __all__ = ["RQPStateData", "simulate", "simulate_batch", "print_stats", "save_logs", "compute_aggregate_statistics",
-           "references", "logs_from_arrays"]
+           "references", "logs_from_arrays", "monte_carlo"]

@@ -59,6 +59,14 @@ def s_off(name: str, n: int) -> int:
     return fn("DAT_S_" + name, n)
 
 
+# ---- episodes (DAT_EP_*: the reasons and the outcome record's words; dat_episode_*, csrc/dat_episode.hpp)
+EP_REASONS = {k[len("DAT_EP_"):]: const(k) for k in ("DAT_EP_NONE", "DAT_EP_DIVERGED", "DAT_EP_COLLISION", "DAT_EP_GOAL",
+                                                     "DAT_EP_STALL", "DAT_EP_TIME_LIMIT")}
+EP_NREASON = const("DAT_EP_NREASON")
+EP_WORDS = const("DAT_EP_WORDS")
+EP = {k[len("DAT_EP_"):]: const(k) for k in ("DAT_EP_SLOT", "DAT_EP_RECORD", "DAT_EP_START", "DAT_EP_END", "DAT_EP_STEPS",
+                                             "DAT_EP_ITMAX", "DAT_EP_RUN", "DAT_EP_MIND", "DAT_EP_XL", "DAT_EP_VL")}
+
 # ---- checkpoint record (DAT_CK_*) and its field table (csrc/dat_ckpt.hpp, the lists the copy kernels are written from)
 CK_HEADER_BYTES = const("DAT_CK_HEADER_BYTES")
 CK_MAGIC = const("DAT_CK_MAGIC")

@@ -336,6 +336,73 @@ int dat_log_read_summary(dat_handle* h, int first, int count, int* iters, double
 int dat_log_clear(dat_handle* h);
 int dat_log_end(dat_handle* h);
 
+/* ---- episodes: scenarios that end and respawn inside the resident loop ------------------------------------------------
+ * The reference's loop flies a fixed time (example/rqp_example.py:120-131); a Monte Carlo campaign wants a scenario to
+ * end -- at its goal, at a collision, in a stall, after a step budget -- to be recorded once with its outcome, and its
+ * slot to take the next initial condition, without a host round trip per step.  While episodes are open on a handle,
+ * dat_closed_loop does this for every scenario at every HL step, after the scenario's control step and before its
+ * rollout: it updates the scenario's accumulators (control steps, sum and maximum of iters, steps at max_iter + 1
+ * passes, the current run of such steps, the smallest min_env_dist), evaluates the rule below (csrc/dat_episode.hpp,
+ * one function for the kernels and the host) on the pre-rollout state, the step's iters, collision flag and
+ * min_env_dist and the accumulators, and where a reason fires it appends an outcome record (csrc/dat_layout.h,
+ * DAT_EP_*) and overwrites the scenario with a record of the pool INSTEAD of rolling it out.  The respawned scenario's
+ * next control step takes its desired acceleration and env rows from the new state, as after dat_checkpoint_load.
+ * The lowest code that fires wins:
+ *   1 DAT_EP_DIVERGED    a word of xl or vl is not finite, or max |xl_c| > bound (+inf: only the first)
+ *   2 DAT_EP_COLLISION   the step's collision flag is set (on_collision != 0)
+ *   3 DAT_EP_GOAL        xl_x >= goal_x (+inf: off)
+ *   4 DAT_EP_STALL       the last stall_steps control steps of the episode each ran max_iter + 1 passes (0: off;
+ *                        refused on centralized handles, which have no passes)
+ *   5 DAT_EP_TIME_LIMIT  the episode has computed max_steps control steps (0: off)
+ * The pool is a checkpoint blob of P >= 1 records (dat_checkpoint_save's format), uploaded once.  dat_episode_begin
+ * loads record s mod P into every slot s (the slot's episode 0; with a pool that is the handle's own checkpoint,
+ * nothing changes); slot s starts its j-th episode, j >= 1, from record (s + j B) mod P, s the scenario's index in
+ * the whole batch and B the batch: no cursor is shared, so results do not depend on the schedule.  With wrap = 0 a slot
+ * whose next index s + j B would reach P takes record s mod P and goes idle: it keeps running, ends no more and
+ * records nothing further (a slot s >= P is idle from the start); idle == B tells the host that every record of the
+ * pool has been run once.
+ * The outcome table holds `capacity` records, appended through one device counter in no fixed order (sort by end tick
+ * and slot).  Beyond the capacity an episode still ends and respawns, the per-reason totals stay exact and `lost`
+ * counts the records dropped.
+ * Works on every schedule of dat_closed_loop, with the serial schedule's results bit for bit; with no episodes open
+ * every launch is the one it was.  Not yet with an open log, DAT_PLANT_RP or tracking records (each an error, in
+ * either order), and dat_checkpoint_load is refused while episodes are open (dat_checkpoint_save is not).
+ * dat_control_step and dat_rollout do not evaluate episodes.
+ * Every argument is checked on the host before anything is copied (csrc/dat_episode_host.hpp): an error leaves no
+ * episodes open and the handle as it was. */
+typedef struct dat_episode_rules {
+  double goal_x;    /* GOAL: xl_x >= goal_x; +inf: off                                          */
+  double bound;     /* DIVERGED: max |xl_c| > bound; +inf: only non-finite words                */
+  int max_steps;    /* TIME_LIMIT after this many control steps; 0: off                         */
+  int stall_steps;  /* STALL after this many consecutive steps at max_iter + 1 passes; 0: off   */
+  int on_collision; /* COLLISION on the step's collision flag                                   */
+  int wrap;         /* next record index modulo P (1), or idle once the pool is used up (0)     */
+} dat_episode_rules;
+void dat_episode_default_rules(dat_episode_rules* rules); /* everything off, wrap = 1 */
+int dat_episode_begin(dat_handle* h, const dat_episode_rules* rules, const void* pool_blob, long long bytes,
+                      int capacity);
+/* ended[DAT_EP_NREASON] (6 words, csrc/dat_layout.h; may be NULL): episodes ended per reason since dat_episode_begin
+ * ([0] unused, 0); records held in the table; records lost to its capacity since the last dat_episode_clear; idle
+ * slots. */
+int dat_episode_counts(dat_handle* h, long long* ended, long long* held, long long* lost, long long* idle);
+/* Held records [first, first + count), in table order; any output may be NULL.  slot, episode, record, reason, steps,
+ * iter_sum, iter_max, full_steps (steps at max_iter + 1 passes), stall_run: count ints each; start_tick, end_tick:
+ * count; min_env_dist: count; xl, vl: count x 3. */
+int dat_episode_read(dat_handle* h, int first, int count, int* slot, int* episode, int* record, int* reason,
+                     long long* start_tick, long long* end_tick, int* steps, int* iter_sum, int* iter_max,
+                     int* full_steps, int* stall_run, double* min_env_dist, double* xl, double* vl);
+/* Empties the table and zeroes `lost`; totals, idle slots and the running episodes stay. */
+int dat_episode_clear(dat_handle* h);
+/* Closes the episodes and frees pool and table: dat_closed_loop is the plain loop again. */
+int dat_episode_end(dat_handle* h);
+/* Per slot (batch ints each, any may be NULL): the pool record its running episode started from, the episodes it has
+ * finished, the control steps of the running episode, and whether it is idle. */
+int dat_episode_slots(dat_handle* h, int* record, int* episodes, int* steps, int* idle);
+/* Respawns since dat_episode_begin by the early pass of the overlapped schedules (0 by construction: the early pass
+ * runs beside the drain that finished the scenario, whose warm state may not be written back yet, and leaves an
+ * ending scenario to the rest pass) and by every other pass; deferred: ending scenarios the early gate left unmarked. */
+int dat_get_episode_respawns(dat_handle* h, long long* early, long long* rest, long long* deferred);
+
 /* ---- counters since the last reset: agent-QP solves, IPM iterations, IPM iterations x active
  * constraint rows (for the flop model of DESIGN.md 3.1), control steps, and the summed device time
  * of the high-level kernels [ms] (HIP events on the handle stream).  Any pointer may be NULL. */
