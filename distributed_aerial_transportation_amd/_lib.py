@@ -17,10 +17,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 LIB_PATH = os.path.join(PKG, "libdat.so")
 CSRC = os.path.join(PKG, "csrc")
-# The library's translation units, compiled in parallel: every .hip under csrc/ -- dat.hip (host side: handle, step
-# chain, C-ABI), the kernel units dat_k_*.hip (csrc/dat_launch.hpp lists them), dat_cent.hip (k_cent<n>), dat_comm.hip
-# (RCCL metric collectives) -- but the unity file, which is all of dat.hip's as one unit for development builds
-# (tools/build_var.sh).
+# The library's translation units, compiled in parallel: every .hip under csrc/ -- the host units dat.hip (handle, step
+# chain, schedules, C-ABI) and dat_h_*.hip (log, episodes, checkpoints), the kernel units dat_k_*.hip
+# (csrc/dat_launch.hpp lists them), dat_cent.hip (k_cent<n>), dat_comm.hip (RCCL metric collectives) -- but the unity
+# file, which is the host and kernel units as one unit for development builds (tools/build_var.sh).
 UNITY = os.path.join(CSRC, "dat_unity.hip")
 SRCS = tuple(sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip") and f != os.path.basename(UNITY)))
 OBJ_DIR = os.path.join(PKG, "build")

@@ -1,5 +1,5 @@
 // dat_episode_host.hpp -- the host-side checks of dat_episode_begin / dat_episode_read (include/dat.h): pure functions
-// of their arguments, run before anything is copied or launched.  Host code only, no HIP: dat.hip includes it, and
+// of their arguments, run before anything is copied or launched.  Host code only, no HIP: dat_h_episode.hip includes it, and
 // tests/episode_host/ep_check_main.cpp compiles it alone.
 #pragma once
 

@@ -32,12 +32,28 @@ def test_deps_cover_csrc_and_the_abi_header():
 def test_unity_file_includes_every_kernel_unit():
     included = set(re.findall(r'^#include "([^"]+\.hip)"', _text(_lib.UNITY), re.M))
     # the kernel units of dat.hip's families are the dat_k_*.hip (csrc/dat_launch.hpp); the centralized kernel and
-    # the collectives are units of their own in every build, and dat.hip holds no kernel
+    # the collectives are units of their own in every build, and the host units (dat.hip, dat_h_*.hip) hold no kernel
     names = {os.path.basename(s) for s in _lib.SRCS}
     kernel_units = {u for u in names if u.startswith("dat_k_")}
     assert kernel_units
-    for u in names - kernel_units - {"dat_cent.hip", "dat_comm.hip"}:
+    host_units = names - kernel_units - {"dat_cent.hip", "dat_comm.hip"}
+    for u in host_units:
         assert "__global__" not in _text(os.path.join(CSRC, u)), u
     assert kernel_units <= included, kernel_units - included
     assert "dat.hip" in names and "dat.hip" in included
+    assert {"dat_h_log.hip", "dat_h_episode.hip", "dat_h_ckpt.hip"} <= host_units
+    assert host_units <= included, host_units - included  # every unit but the two that stand alone
+    assert included <= names, included - names
     assert re.search(r"^#define DAT_UNITY\b", _text(_lib.UNITY), re.M)
+
+
+def test_rule_and_handle_headers_stay_with_the_host_units():
+    """dat_modes.hpp and dat_handle.hpp are host code: no kernel unit, and no header a kernel unit includes, includes
+    them; dat_modes.hpp includes nothing of HIP's"""
+    names = {os.path.basename(s) for s in _lib.SRCS}
+    host = {"dat.hip", "dat_unity.hip", "dat_handle.hpp"} | {u for u in names if u.startswith("dat_h_")}
+    for f in os.listdir(CSRC):
+        if f not in host:
+            assert not re.search(r'#include "dat_(modes|handle)\.hpp"', _text(os.path.join(CSRC, f))), f
+    modes = _text(os.path.join(CSRC, "dat_modes.hpp"))
+    assert "hip" not in re.sub(r"//.*", "", modes).lower()

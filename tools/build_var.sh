@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of libdat.so with extra compile flags into build_var/libdat_<name>.so (CPU side, for
-# tools/ab_bench.sh on the GPU box).  The flags go to csrc/dat_unity.hip -- dat.hip and the kernel units as one
+# tools/ab_bench.sh on the GPU box).  The flags go to csrc/dat_unity.hip -- the host and the kernel units as one
 # translation unit, which the builds with device globals need (-DDAT_ITER_HIST, -DDAT_PHASE_PROF,
 # -DDAT_CAPTURE_LOOSE) and every other variant may use; the centralized kernel's and the collectives' objects are
 # compiled once into build_var/.
