@@ -239,6 +239,12 @@ class BatchedController:
         L.check(self._lib.dat_cadmm_slots(self._h, int(self.batch if batch is None else batch), ctypes.byref(g)))
         return g.value
 
+    def debug_row_modes(self, modes: Optional[Tuple[int, int, int]]) -> None:
+        """dat_debug_row_modes (tests): run k_cadmm with the row modes (m0, m1, m2) of env classes 0-2 instead of the
+        rule's; None returns to the rule.  A triple k_cadmm is not built for raises DatError."""
+        m0, m1, m2 = (-1, -1, -1) if modes is None else (int(m) for m in modes)
+        L.check(self._lib.dat_debug_row_modes(self._h, m0, m1, m2))
+
     def reset_warm_start(self) -> None:
         L.check(self._lib.dat_reset_warm_start(self._h))
 

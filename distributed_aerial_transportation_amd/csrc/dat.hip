@@ -55,13 +55,21 @@ namespace {
 // tail stream, started with k_cadmm (their lists are known after k_bucket), and the hand-over lists after
 // k_cadmm on the step's stream, which then waits for the first.
 constexpr int TAIL_BLOCKS = 256;
+constexpr size_t CADMM_LDS_MAX = 64 * 1024;  // dynamic LDS of a k_cadmm workgroup without a raised limit
 // (KArgs::done set: the ADV instantiations, dat_closed_loop's overlap)
 int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st) {
   KArgs r = a;
   r.G = 1;
   const bool adv = a.done != nullptr;
-  const auto kc = adv ? launch_k_cadmm_adv : launch_k_cadmm;  // (forest, blocks, LDS bytes, stream, arguments)
+  const auto kc = adv ? launch_k_cadmm_adv : launch_k_cadmm;  // (forest, row modes, blocks, LDS bytes, stream, arguments)
   const auto kt = launch_k_cadmm_tail;
+  // the row modes of the launch, stated once: the kernel instantiation and the carve's bytes both go by this word
+  // (the rule's, cadmm_row_modes; dat_debug_row_modes: a forced one)
+  const int rms = h->force_rms >= 0 ? h->force_rms : cadmm_row_modes(a.n, a.G);
+  const int max_cls = h->nforest > 0 ? NCLS - 1 : 0;
+  const size_t lds = cadmm_lds_bytes_of(a.n, a.G, max_cls, rms);
+  if (!cadmm_rms_built(rms)) return fail("k_cadmm: no instantiation of the launch's row modes");
+  if (lds > CADMM_LDS_MAX) return fail("k_cadmm: the forced row modes' carve exceeds a workgroup's dynamic LDS");
   if (h->nforest > 0) {
     if (a.route) {
       KArgs t = r;
@@ -72,11 +80,11 @@ int launch_cadmm(const dat_handle* h, const KArgs& a, int blocks, hipStream_t st
       HIPCHK(kt(true, TAIL_BLOCKS, cadmm_tail_lds_bytes(a.n, NCLS - 1), ts, t));
       HIPCHK(hipEventRecord(h->tail.ev[1], ts));
     }
-    HIPCHK(kc(true, blocks, cadmm_lds_bytes(a.n, a.G, NCLS - 1), st, a));
+    HIPCHK(kc(true, rms, blocks, lds, st, a));
     HIPCHK(kt(true, TAIL_BLOCKS, cadmm_tail_lds_bytes(r.n, NCLS - 1), st, r));
     if (a.route) HIPCHK(hipStreamWaitEvent(st, h->tail.ev[1], 0));
   } else {
-    HIPCHK(kc(false, blocks, cadmm_lds_bytes(a.n, a.G, 0), st, a));
+    HIPCHK(kc(false, rms, blocks, lds, st, a));
     HIPCHK(kt(false, TAIL_BLOCKS, cadmm_tail_lds_bytes(r.n, 0), st, r));
   }
   return 0;
@@ -637,6 +645,14 @@ int dat_create(const dat_config* cfg, dat_handle** out) {
     dat_destroy(h);
     return fail("dat_create: tail kernel LDS attribute");
   }
+  // every row-mode word the rule can give this team (G: by the batch, cadmm_slots) has its k_cadmm instantiation
+  if (c.mode == DAT_MODE_CADMM)
+    for (int G = 1; G <= 64 / c.n; ++G)
+      if (!cadmm_rms_built(cadmm_row_modes(c.n, G))) {
+        dat_destroy(h);
+        return fail("dat_create: k_cadmm is not built for the row modes of n = " + std::to_string(c.n) + " at " +
+                    std::to_string(G) + " scenario slots (DAT_CADMM_RMS, dat_cadmm_lds.hpp)");
+      }
   // LDS budgets
   size_t lds = c.mode == DAT_MODE_CADMM ? cadmm_lds_bytes(c.n, 64 / c.n) : (c.mode == DAT_MODE_DD ? dd_setup_lds(c.n) : 0);
   if (lds > 160 * 1024) {
@@ -1136,6 +1152,20 @@ int dat_cadmm_slots(dat_handle* h, int batch, int* slots) {
   if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_cadmm_slots: C-ADMM handles only");
   if (batch < 1 || !slots) return fail("dat_cadmm_slots: batch must be positive and slots non-null");
   *slots = cadmm_slots(h, batch, h->cfg.n);
+  return 0;
+}
+
+int dat_debug_row_modes(dat_handle* h, int m0, int m1, int m2) {
+  if (!h) return fail("dat_debug_row_modes: null handle");
+  if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_debug_row_modes: C-ADMM handles only");
+  if (m0 < 0 && m1 < 0 && m2 < 0) {
+    h->force_rms = -1;
+    return 0;
+  }
+  if (m0 < 0 || m0 > 2 || m1 < 0 || m1 > 2 || m2 < 0 || m2 > 2) return fail("dat_debug_row_modes: modes are 0, 1 or 2");
+  if (!cadmm_rms_built(rm_pack(m0, m1, m2)))
+    return fail("dat_debug_row_modes: k_cadmm is not built for these row modes (DAT_CADMM_RMS)");
+  h->force_rms = rm_pack(m0, m1, m2);
   return 0;
 }
 

@@ -1,5 +1,5 @@
-// dat_cadmm_drain.hpp -- the C-ADMM drain (cadmm_drain<CLS, RB, ADV>), its LDS carve and the kernel templates
-// k_cadmm<ADV> / k_cadmm0<ADV>.  Three units instantiate it, each a share of the device code that compiles beside the
+// dat_cadmm_drain.hpp -- the C-ADMM drain (cadmm_drain<CLS, RB, ADV, RMODE>), its LDS carve and the kernel templates
+// k_cadmm<ADV, RMS> / k_cadmm0<ADV, RM0>.  Three units instantiate it, each a share of the device code that compiles beside the
 // others: dat_k_cadmm.hip (ADV = false), dat_k_cadmm_adv.hip (ADV = true) and dat_k_cadmm_tail.hip (RB = true).
 #pragma once
 
@@ -67,8 +67,15 @@ __device__ inline CadmmLds cadmm_carve(double* smem, int n, int G, int cls, int 
 // ipmx are stored write-through and stamped in KArgs::done, and k_cadmm's class-0 drain tells the host when its
 // queue has been claimed empty.  Without it k_cadmm / k_cadmm0 are compiled without any of that; the tail kernels
 // exist once and go by KArgs::done at run time (a second instantiation changes how their solver is inlined).
-template <int CLS, bool RB, bool ADV>
+// RMODE: the row placement of the class's IPM (dat_cadmm_lds.hpp: 0 registers, 1 LDS rows, 2 LDS rows + the class's
+// aux slots; the tail: 3), fixed at compile time -- the drain carries the one ipm_solve instantiation it runs, and
+// the host launches the kernel of the word it sized the carve by (cadmm_row_modes, launch_cadmm).
+template <int CLS, bool RB, bool ADV, int RMODE>
 __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
+  static_assert(RB ? RMODE == 3 : RMODE >= 0 && RMODE <= 2, "row mode");
+  static_assert(RB || RMODE == 0 || CLS < NCLS - 1, "class 3 keeps its rows in registers");
+  static_assert(RMODE != 2 || cadmm_auxm(CLS) != 0, "mode 2 needs aux slots");
+  static_assert(RB || RMODE != 1 || CLS >= ROWLDS_MIN_CLS, "LDS rows without aux slots: classes ROWLDS_MIN_CLS up");
   constexpr bool ENV = CLS > 0;
   constexpr int NR = cadmm_nr(CLS);
   constexpr int NE = class_env_rows(CLS);
@@ -96,8 +103,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
   }
   int* const qh = a.scount + sc_at(TM ? SC_TAIL_HEAD : RB ? SC_HAND_HEAD : SC_HEAD, CLS);
   const int* const ql = (RB && !TM ? a.rlist : a.slist) + first;
-  const int rmode = RB ? 3 : cadmm_row_mode(n, G, CLS);  // wave-uniform
-  CadmmLds L = cadmm_carve(smem, n, G, CLS, rmode);
+  CadmmLds L = cadmm_carve(smem, n, G, CLS, RMODE);
   double* fb = L.fbar + lsc * N3;
   double* rts = L.Rt + lsc * RT_STRIDE * n;
   double* myred = L.red + lane * RDS;
@@ -122,6 +128,9 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
   int kstep = 0;  // fused control steps (dat_control_steps): the slot scenario's current step
   int rmask = -1;  // k_cadmm_tail: the lanes that solve in the current pass (a resumed pass: those handed over)
   double rho = a.rho0;
+  // the slot's QPShared is to be built at the top of the next pass: a new scenario, or a fused next step of the
+  // same one.  One site, so build_shared_inl is inlined once and both compute the same bits.
+  bool rebuild = false;
   WaveCounters wc;
   for (;;) {
     // ---- refill empty slots from the queue
@@ -171,8 +180,13 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
         for (int q = 0; q < iter; ++q) rho = fmin(rho * a.tau, a.rho_max);  // the pass's rho, as k_cadmm had it
         qstat = a.qstatus[(size_t)sc * n + i];  // the pass's status of a lane not solved again
       }
+      rebuild = true;
+    }
+    if (rebuild) {
+      rebuild = false;
       if (i == 0 && vi == 0)
-        build_shared(S, prm, n, st, a.acc + ((size_t)kstep * a.B + sc) * 6, prm[DAT_P_KFD], prm[DAT_P_KMD], 3, true);
+        build_shared_inl(S, prm, n, a.state + (size_t)sc * a.S, a.acc + ((size_t)kstep * a.B + sc) * 6,
+                         prm[DAT_P_KFD], prm[DAT_P_KMD], 3, true);
     }
     if (!__syncthreads_or(slot_sc >= 0)) break;  // every slot retired
     DAT_PHASE(12);
@@ -240,16 +254,12 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
           }
         }
 #endif
-      } else if constexpr (CLS < NCLS - 1 && (CLS >= ROWLDS_MIN_CLS || AUXM != 0)) {
-        if (AUXM != 0 && rmode == 2)
-          o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowLds, AUXM, NoGrp, RM>(
-              shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowLds{L.rows, lane});
-        else if (CLS >= ROWLDS_MIN_CLS && rmode == 1)
-          o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowLds, 0, NoGrp, RM>(
-              shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowLds{L.rows, lane});
-        else
-          o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowRegs, 0, NoGrp, RM>(
-              shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol);
+      } else if constexpr (RMODE == 2) {
+        o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowLds, AUXM, NoGrp, RM>(
+            shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowLds{L.rows, lane});
+      } else if constexpr (RMODE == 1) {
+        o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowLds, 0, NoGrp, RM>(
+            shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol, RowLds{L.rows, lane});
       } else {
         o = ipm_solve<MODE_CADMM, 1, NR, SHT, ERT, RtLds, RowRegs, 0, NoGrp, RM>(
             shr, err, rtr, P, prm + DAT_P_FEQ(n) + 3 * i, y, w, bst, IPM_MAX_ITER, a.qp_tol);
@@ -390,11 +400,8 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
           qstat = ST_OPTIMAL;
           rho = a.rho0;
           if (RB) wrl[0] = 0.0;
-          if (i == 0 && vi == 0) {
-            build_shared(S, prm, n, a.state + (size_t)sc * a.S, a.acc + ((size_t)kstep * a.B + sc) * 6,
-                         prm[DAT_P_KFD], prm[DAT_P_KMD], 3, true);
-            L.wmx[ls] = 0;
-          }
+          rebuild = true;  // (the shared data of the step: at the top of the next pass)
+          if (i == 0 && vi == 0) L.wmx[ls] = 0;
         } else if (i == 0) {
           L.sid[ls] = -1;
         }
@@ -428,19 +435,35 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
 // instantiation of the IPM.  All wavefronts work on the same class at (nearly) the same time: the
 // unrolled IPM of one class is ~80-130 KB of code, and wavefronts of different classes sharing a
 // CU's instruction cache measured 16 % slower (proportional class starts: 12.9 vs 11.1 ms, C4 path).
-template <bool ADV>
+// RMS: the row modes of classes 0 .. 2 (rm_pack); the host launches the instantiation of the launch's word.
+template <bool ADV, int RMS>
 __global__ __launch_bounds__(64) void k_cadmm(KArgs a) {
-  cadmm_drain<3, false, ADV>(a);
-  cadmm_drain<2, false, ADV>(a);
-  cadmm_drain<1, false, ADV>(a);
-  cadmm_drain<0, false, ADV>(a);
+  cadmm_drain<3, false, ADV, 0>(a);
+  cadmm_drain<2, false, ADV, rm_of(RMS, 2)>(a);
+  cadmm_drain<1, false, ADV, rm_of(RMS, 1)>(a);
+  cadmm_drain<0, false, ADV, rm_of(RMS, 0)>(a);
 }
 // Without a forest every scenario is in env class 0 (k_env_class finds no tree): the class-0 drain in a
 // kernel of its own, with a 960 B/lane scratch frame instead of k_cadmm's 1,728 (same arithmetic).  C5
 // 84.2 / 84.1 -> 80.3 / 79.9 ms per step, C2 12.7 / 12.9 -> 12.0 / 12.1 (round 4, kernel-trace A/B).
 // With a forest one launch per class measured 2x slower on C4 (each class launch drains to its own
 // tail): k_cadmm keeps the four drains in one launch there.
+template <bool ADV, int RM0>
+__global__ __launch_bounds__(64) void k_cadmm0(KArgs a) { cadmm_drain<0, false, ADV, RM0>(a); }
+
+// The launch of a unit's drain kernels (ADV: the unit's): the instantiation of the word rms, one per word of
+// DAT_CADMM_RMS -- k_cadmm0 by class 0's mode alone.  A word that is not built is refused (dat_create and
+// dat_debug_row_modes refuse it before: cadmm_rms_built).
 template <bool ADV>
-__global__ __launch_bounds__(64) void k_cadmm0(KArgs a) { cadmm_drain<0, false, ADV>(a); }
+inline hipError_t launch_k_cadmm_of(bool forest, int rms, int blocks, size_t lds, hipStream_t st, const KArgs& a) {
+  void (*k)(KArgs) = nullptr;
+#define DAT_X(m0, m1, m2) \
+  if (rms == rm_pack(m0, m1, m2)) k = forest ? k_cadmm<ADV, rm_pack(m0, m1, m2)> : k_cadmm0<ADV, m0>;
+  DAT_CADMM_RMS(DAT_X)
+#undef DAT_X
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(64), lds, st, a);
+  return hipGetLastError();
+}
 
 }  // namespace

@@ -56,7 +56,7 @@ __host__ __device__ constexpr int cadmm_nr(int cls) { return NBASE + class_env_r
 // G: scenario slots per wavefront (cadmm_slots)
 // per-slot ints done / sid / wmx (G each), rounded to 16 bytes
 __host__ __device__ constexpr int slot_ints(int G) { return (3 * G + 3) & ~3; }
-__host__ __device__ inline size_t cadmm_fixed_bytes(int n, int G) {
+__host__ __device__ constexpr size_t cadmm_fixed_bytes(int n, int G) {
   return sizeof(double) * (al2((size_t)G * 3 * n) + (size_t)G * RT_STRIDE * n) + sizeof(QPShared) * (size_t)G +
          sizeof(int) * (size_t)slot_ints(G);
 }
@@ -74,7 +74,7 @@ constexpr unsigned TAIL_AUXM = 15u;
 __host__ __device__ constexpr int cadmm_aux_doubles(int cls, int rmode) {
   return rmode == 2 ? ipm_aux_doubles(1, cadmm_auxm(cls)) : rmode == 3 ? ipm_aux_doubles(1, TAIL_AUXM) : 0;
 }
-__host__ __device__ inline size_t cadmm_area_doubles(int cls, int rmode) {
+__host__ __device__ constexpr size_t cadmm_area_doubles(int cls, int rmode) {
   const size_t rows = rmode ? (size_t)row_lds_doubles(cadmm_nr(cls), cadmm_aux_doubles(cls, rmode)) : 0;
   return (rows > 64 * RDS ? rows : 64 * RDS) + (size_t)env_lds_doubles(class_env_rows(cls));
 }
@@ -83,7 +83,7 @@ __host__ __device__ inline size_t cadmm_area_doubles(int cls, int rmode) {
 // are cheaper in registers: an LDS row access costs an LDS round trip, which pays only once the rows
 // would otherwise spill.
 constexpr int ROWLDS_MIN_CLS = 1;
-__host__ __device__ inline int cadmm_row_mode(int n, int G, int cls) {
+__host__ __device__ constexpr int cadmm_row_mode(int n, int G, int cls) {
   if (cls >= NCLS - 1) return 0;
   if (cadmm_auxm(cls) && cadmm_fixed_bytes(n, G) + sizeof(double) * cadmm_area_doubles(cls, 2) <= LDS_WAVE_BUDGET)
     return 2;
@@ -91,15 +91,45 @@ __host__ __device__ inline int cadmm_row_mode(int n, int G, int cls) {
     return 1;
   return 0;
 }
+// The row modes of a launch, classes 0 .. 2 in two bits each (class 3: always registers).  The mode is a template
+// parameter of the drain (cadmm_drain<CLS, ., ., RMODE>: each class drain carries the one IPM instantiation it runs),
+// so a launch picks the k_cadmm / k_cadmm0 instantiation of its word: cadmm_row_modes(n, G), the rule above, which
+// sizes the carve too -- kernel and carve go by the same word (launch_cadmm, dat.hip).
+__host__ __device__ constexpr int rm_pack(int m0, int m1, int m2) { return m0 | (m1 << 2) | (m2 << 4); }
+__host__ __device__ constexpr int rm_of(int rms, int cls) { return cls >= NCLS - 1 ? 0 : (rms >> (2 * cls)) & 3; }
+__host__ __device__ constexpr int cadmm_row_modes(int n, int G) {
+  return rm_pack(cadmm_row_mode(n, G, 0), cadmm_row_mode(n, G, 1), cadmm_row_mode(n, G, 2));
+}
+// The words the kernel units instantiate (DAT_CADMM_RMS: one line per word, in launchers and here): every word the
+// rule gives for 3 <= n <= NMAX and 1 <= G <= 64 / n.  Classes 0 and 1 always fit with their aux slots; class 2
+// loses them where the fixed part is large (n = 3 .. 5 at the largest G).
+#define DAT_CADMM_RMS(X) X(2, 2, 2) X(2, 2, 1)
+__host__ __device__ constexpr bool cadmm_rms_built(int rms) {
+#define DAT_X(m0, m1, m2) if (rms == rm_pack(m0, m1, m2)) return true;
+  DAT_CADMM_RMS(DAT_X)
+#undef DAT_X
+  return false;
+}
+__host__ __device__ constexpr bool cadmm_rms_cover(int nmax) {
+  for (int n = 3; n <= nmax; ++n)
+    for (int G = 1; G <= 64 / n; ++G)
+      if (!cadmm_rms_built(cadmm_row_modes(n, G))) return false;
+  return true;
+}
+static_assert(cadmm_rms_cover(NMAX), "cadmm_row_mode gives a word DAT_CADMM_RMS does not list");
 // dynamic LDS of a k_cadmm workgroup: the largest carve of the env classes that can occur (without a
-// forest every scenario is class 0, so the launch needs only that carve and more workgroups fit a CU)
-__host__ __device__ inline size_t cadmm_lds_bytes(int n, int G, int max_cls = NCLS - 1) {
+// forest every scenario is class 0, so the launch needs only that carve and more workgroups fit a CU), by the
+// launch's row modes
+__host__ __device__ constexpr size_t cadmm_lds_bytes_of(int n, int G, int max_cls, int rms) {
   size_t m = 0;
   for (int c = 0; c <= max_cls; ++c) {
-    const size_t b = cadmm_fixed_bytes(n, G) + sizeof(double) * cadmm_area_doubles(c, cadmm_row_mode(n, G, c));
+    const size_t b = cadmm_fixed_bytes(n, G) + sizeof(double) * cadmm_area_doubles(c, rm_of(rms, c));
     m = b > m ? b : m;
   }
   return m;
+}
+__host__ __device__ constexpr size_t cadmm_lds_bytes(int n, int G, int max_cls = NCLS - 1) {
+  return cadmm_lds_bytes_of(n, G, max_cls, cadmm_row_modes(n, G));
 }
 // dynamic LDS of a k_cadmm_tail workgroup (one scenario slot, rmode 3), with the n lanes' IPM scratch records
 // (best iterate, stiff-row columns and Schur factor: best_size(1) doubles each) behind the class's area: the

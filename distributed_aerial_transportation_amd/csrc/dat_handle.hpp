@@ -86,6 +86,7 @@ struct dat_handle {
   hipEvent_t ek = nullptr;       // C-ADMM: after k_bucket
   double cadmm_ms = 0.0;         // summed device time of k_cadmm
   int persistent_blocks = 1024;  // C-ADMM: resident k_cadmm blocks (CUs x 4 wavefronts)
+  int force_rms = -1;            // dat_debug_row_modes: k_cadmm's row modes (rm_pack) instead of the rule's; -1: the rule's
   double qp_tol = IPM_TOL;       // IPM stopping tolerance (dat_set_qp_tolerance)
   double* params = nullptr;
   int ppp = 0;

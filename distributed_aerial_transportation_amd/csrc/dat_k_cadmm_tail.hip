@@ -20,13 +20,13 @@ namespace {
 // start and stall exit of the tail rule's passes.  A kernel of its own: the robust solver compiled into k_cadmm
 // cost the fast path 36-60 % (register allocation, C4 A/B).  Without a listed scenario its blocks return at once.
 __global__ __launch_bounds__(64) void k_cadmm_tail(KArgs a) {
-  cadmm_drain<3, true, false>(a);
-  cadmm_drain<2, true, false>(a);
-  cadmm_drain<1, true, false>(a);
-  cadmm_drain<0, true, false>(a);
+  cadmm_drain<3, true, false, 3>(a);
+  cadmm_drain<2, true, false, 3>(a);
+  cadmm_drain<1, true, false, 3>(a);
+  cadmm_drain<0, true, false, 3>(a);
 }
 // (without a forest: the class-0 drain alone, as k_cadmm0)
-__global__ __launch_bounds__(64) void k_cadmm0_tail(KArgs a) { cadmm_drain<0, true, false>(a); }
+__global__ __launch_bounds__(64) void k_cadmm0_tail(KArgs a) { cadmm_drain<0, true, false, 3>(a); }
 
 // the kernel's argument type, named as it was when the kernel got its symbol: dat::AgentQPArgs's fields
 struct AgentQPArgs : dat::AgentQPArgs {

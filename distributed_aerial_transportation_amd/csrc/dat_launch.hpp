@@ -1,19 +1,20 @@
 // dat_launch.hpp -- the seam between dat.hip (handle, step chain, C-ABI: host code only) and the kernel units
 // beside it, one per kernel family, which compile in parallel:
-//   dat_k_cadmm.hip       k_cadmm<false>, k_cadmm0<false>; k_dd<false>
-//   dat_k_cadmm_adv.hip   k_cadmm<true>, k_cadmm0<true> (the closed loop's advance overlap); k_dd<true>
+//   dat_k_cadmm.hip       k_cadmm<false, .>, k_cadmm0<false, .> (one per row-mode word, DAT_CADMM_RMS); k_dd<false>
+//   dat_k_cadmm_adv.hip   k_cadmm<true, .>, k_cadmm0<true, .> (the closed loop's advance overlap); k_dd<true>
 //   dat_k_cadmm_tail.hip  k_cadmm_tail, k_cadmm0_tail, the raise of their dynamic-LDS limit; k_agent_qp
 //   dat_k_dd.hip          k_dd_setup<0, 3..8>, k_dd_key, the byte counts of the DD carves
 //   dat_k_step.hip        the rollout / advance family as a whole (the inliner's choices for the device functions it
 //                         shares depend on the callers the unit holds), the sorts, k_warm, k_env, the rigid-payload,
 //                         PMRL and checkpoint kernels
-// Why the kernels that solve agent QPs are grouped so: they all call build_shared (dat_qp.hpp), which stays out of
-// line.  A unit's device code is optimised as a whole with every function but the kernels internal, so a unit whose
-// callers all pass build_shared the same constant (cadmm = true from the C-ADMM drains, false from k_dd) gets it
-// specialised, and its callers a register allocation fitted to that version: kernels that differ from those of the
-// one unit they came from.  Each unit that calls it therefore holds callers of both kinds -- a C-ADMM drain with a
-// k_dd instantiation, the tail kernels with k_agent_qp, which passes a run-time value (and runs the tail's robust
-// solver) -- and every kernel comes out instruction for instruction as before (tools/same_kernels.py).
+// Why the kernels that solve agent QPs are grouped so: the split placed them so that every unit calling the
+// out-of-line build_shared (dat_qp.hpp) held callers that pass it different constants (cadmm = true from the C-ADMM
+// drains, false from k_dd), which kept the compiler from specialising it per unit.  The C-ADMM drains build inline
+// now (build_shared_inl, one site: the drain kernels hold no call), so the out-of-line function's callers are k_dd in
+// the two drain units, where it is specialised for cadmm = false, and k_agent_qp in the tail unit, which passes a
+// run-time value: the function differs between the units (tools/same_kernels.py reports it SPLIT) and k_dd's
+// register allocation follows its version.  The arithmetic is the text's in each: -ffp-contract=on fuses within
+// an expression only.  The grouping stays for the balance of the units' compile times (profiles/tu_split.md).
 // Each unit exports thin launchers, as dat_cent.hip does (launch_cent, dat_kargs.hpp): one kernel launch each, on the
 // caller's grid, LDS bytes and stream, the instantiation picked by the selectors (adv, forest, env, n); they hold
 // no state, know nothing of the handle and return the launch's error (hipGetLastError).  Every sequence of
@@ -110,9 +111,12 @@ struct EpArgs {
 };
 struct NoEp {};
 
-// ---- dat_k_cadmm.hip, dat_k_cadmm_adv.hip: forest ? k_cadmm<ADV> : k_cadmm0<ADV>, ADV the unit's; k_dd<false>, k_dd<true>
-hipError_t launch_k_cadmm(bool forest, int blocks, size_t lds, hipStream_t st, const KArgs& a);
-hipError_t launch_k_cadmm_adv(bool forest, int blocks, size_t lds, hipStream_t st, const KArgs& a);
+// ---- dat_k_cadmm.hip, dat_k_cadmm_adv.hip: forest ? k_cadmm<ADV, rms> : k_cadmm0<ADV, class 0's mode>, ADV the unit's;
+// k_dd<false>, k_dd<true>
+// rms: the launch's row modes (rm_pack, dat_cadmm_lds.hpp), the word `lds` was sized by: the instantiation of that word
+// (hipErrorInvalidValue: the word is not built)
+hipError_t launch_k_cadmm(bool forest, int rms, int blocks, size_t lds, hipStream_t st, const KArgs& a);
+hipError_t launch_k_cadmm_adv(bool forest, int rms, int blocks, size_t lds, hipStream_t st, const KArgs& a);
 hipError_t launch_k_dd(int blocks, size_t lds, hipStream_t st, const KArgs& a);
 hipError_t launch_k_dd_env(int blocks, size_t lds, hipStream_t st, const KArgs& a);
 // ---- dat_k_cadmm_tail.hip: forest ? k_cadmm_tail : k_cadmm0_tail; k_agent_qp

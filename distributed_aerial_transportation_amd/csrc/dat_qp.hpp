@@ -239,13 +239,16 @@ constexpr int TAIL_PREV = 20, TAIL_PASS = 16;
 // ------------------------------------------------------------------ shared data
 // k_f, k_m: total force / moment weights; variants: bit 0 build C[0] (kdv = 0), bit 1 build C[1]
 // (kdv = 1).  with_K: C-ADMM aggregate over all agents.
-// Not inlined: the drains call it from two sites (a slot's new scenario, and a fused next step,
-// dat_control_steps), and one compiled body keeps the two bitwise identical (inlined copies may contract
-// multiply-adds differently).  Once per scenario and step: the call costs nothing measurable.
-__host__ __device__ inline __attribute__((noinline)) void build_shared(QPShared& S, const double* prm, int n,
-                                                                        const double* st, const double* acc,
-                                                                        double k_f, double k_m, int variants,
-                                                                        bool with_K) {
+// build_shared_inl is the text, inlined where it stands: the C-ADMM drains build at one site (cadmm_drain: a slot's new
+// scenario and a fused next step both go through the top of the pass), so their kernels hold no call -- a call in
+// the persistent loop makes the register allocator save and restore the drain's state around it.  build_shared is
+// the same text out of line, for the callers with more than one site (the DD drain: a new scenario, and a fused
+// next step) and the host builds: one compiled body keeps a unit's sites bitwise identical.  -ffp-contract=on fuses
+// multiply-adds within an expression only, so the inlined and the out-of-line text compute the same bits.
+__host__ __device__ inline __attribute__((always_inline)) void build_shared_inl(QPShared& S, const double* prm, int n,
+                                                                                 const double* st, const double* acc,
+                                                                                 double k_f, double k_m, int variants,
+                                                                                 bool with_K) {
   const double mT = prm[DAT_P_MT];
   const double* xc = prm + DAT_P_XCOM;
   const double* JT = prm + DAT_P_JT;
@@ -344,6 +347,12 @@ __host__ __device__ inline __attribute__((noinline)) void build_shared(QPShared&
     S.rows[l][3] = beta[l] + dot3(al[l], l < NWROW ? bw : bv);
     S.bmask |= 1 << l;
   }
+}
+__host__ __device__ inline __attribute__((noinline)) void build_shared(QPShared& S, const double* prm, int n,
+                                                                        const double* st, const double* acc,
+                                                                        double k_f, double k_m, int variants,
+                                                                        bool with_K) {
+  build_shared_inl(S, prm, n, st, acc, k_f, k_m, variants, with_K);
 }
 
 // env rows (dvl): lhs . dvl >= rhs  <=>  lhs . lin_v(u) + (lhs . bv - rhs) >= 0.  Rows the

@@ -431,6 +431,11 @@ int dat_set_persistent_blocks(dat_handle* h, int blocks);
  * the class's auxiliary slots -- or -1 on arguments out of range.  Tests use the two to build the smallest batch
  * that reaches every instantiation. */
 int dat_cadmm_slots(dat_handle* h, int batch, int* slots);
+/* Tests: run k_cadmm / k_cadmm0 with the row modes (m0, m1, m2) of env classes 0, 1, 2 instead of those
+ * dat_cadmm_row_mode gives, the LDS carve sized by them; (-1, -1, -1) returns to the rule.  k_cadmm is compiled for
+ * the mode triples the rule can give only: any other is refused here, and a control step whose carve by the forced
+ * modes would exceed a workgroup's dynamic LDS fails without a launch.  Results do not depend on the modes. */
+int dat_debug_row_modes(dat_handle* h, int m0, int m1, int m2);
 int dat_cadmm_row_mode(int n, int slots, int env_class);
 /* Summed device time [ms] since the last counter reset of the main solver kernel of each control step:
  * k_cadmm (C-ADMM) or k_dd (DD; the per-scenario quasi-Newton setup k_dd_setup excluded), 0 for
