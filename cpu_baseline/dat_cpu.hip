@@ -19,7 +19,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../distributed_aerial_transportation_amd/csrc/dat_cadmm_step.hpp"
+#include "../distributed_aerial_transportation_amd/csrc/dat_cadmm_host.hpp"
 
 using namespace dat;
 
@@ -28,7 +28,7 @@ long long g_ith[2][8][32];  // tools/ipm_stats.py: IPM iterations by start and a
 #endif
 
 namespace {
-constexpr int NMAXC = 16;
+constexpr int NMAXC = CADMM_HOST_NMAX;
 
 struct Ctx {
   int n, B, P, S;
@@ -38,11 +38,12 @@ struct Ctx {
   long long qp = 0, ipm = 0;
 };
 
-// One C-ADMM control step of scenario sc (control/rqp_cadmm.py:631-675).
+// One C-ADMM control step of scenario sc: the desired acceleration, then the host step (dat_cadmm_host.hpp) on the
+// scenario's forest, with the defaults of dat_default_config and the GPU's tail rule.
 void cadmm_step(Ctx& c, int sc, long long* qp, long long* ipm) {
   const int n = c.n, N3 = 3 * n;
   const double* prm = c.params.data();
-  double* st = c.state.data() + (size_t)sc * c.S;
+  const double* st = c.state.data() + (size_t)sc * c.S;
   const double* trees = nullptr;
   int nt = 0;
   const double* mnt = nullptr;
@@ -55,69 +56,21 @@ void cadmm_step(Ctx& c, int sc, long long* qp, long long* ipm) {
   }
   double acc[6];
   desired_accel_forest(st, n, mnt ? mnt : m0, 1.5, acc);
-  QPShared S;
-  build_shared(S, prm, n, st, acc, prm[DAT_P_KFD], prm[DAT_P_KMD], 3, true);
-  double Rt_all[NMAXC * 9];
-  for (int j = 0; j < n; ++j) make_Rt(prm + DAT_P_RCOM(n) + 3 * j, st + DAT_S_RL(n), Rt_all + 9 * j);
-  QPLane<1> P[NMAXC];
-  EnvRows E[NMAXC];
-  for (int i = 0; i < n; ++i) {
-    lane_cadmm_static(P[i], prm, i);
-    unsigned emask = 0;
-    double lhs[DAT_NENV][3], rhs[DAT_NENV];
-    env_rows(prm, n, st, trees, nt, i, prm[DAT_P_AENVD], &emask, lhs, rhs);
-    set_env_rows(P[i], E[i], S, emask, lhs, rhs);
-    // rows certified infeasible are held (the GPU's tail certifies them once per scenario-step)
-    cadmm_certify_rows(P[i], PlainRef<QPShared>{&S}, EnvPlain{&E[i]});
-  }
-  double* cf = c.cf.data() + (size_t)sc * n * N3;
-  double* fb = c.cfbar.data() + (size_t)sc * N3;
-  double* lam = c.clam.data() + (size_t)sc * n * N3;
-  const double* feq = prm + DAT_P_FEQ(n);
-  const double tol = 1e-2, rho0 = 1.0, tau = 1.0, rho_max = 2.0;
-  const int max_iter = 100;
-  double rho = rho0;
-  int it = 0;
-  const int prev_it = c.iters[sc];  // the previous step's ADMM iterations
-  // the GPU's tail rule (dat_cadmm_step.hpp, with a forest): the warm start and stall exit of the passes it names;
-  // the passes the tail kernel runs keep the agent QPs' warm-start records (tail_keeps_records: from the step's
-  // start when routed, from the first unclean pass or TAIL_PASS)
-  const int tprev = c.nforest > 0 ? TAIL_PREV : 1 << 30, tpass = c.nforest > 0 ? TAIL_PASS : 1 << 30;
-  double wrec[NMAXC][WREC_SIZE];
-  for (int i = 0; i < n; ++i) wrec[i][0] = 0.0;
-  bool in_tail = tail_wedged(prev_it, tprev);
-  for (;;) {
-    in_tail = tail_keeps_records(in_tail, it, tpass);
-    const bool wson = tail_rule(it, prev_it, tprev, tpass);
-    bool unclean = false;
-    for (int i = 0; i < n; ++i) {
-      lane_cadmm_dynamic(P[i], prm, n, i, Rt_all, lam + i * N3, fb, rho);
-      P[i].tuned = cadmm_tuned_start(it, prev_it);  // as k_cadmm
-      double y[1][3], w[6], best[best_size(1)];
-      IPMOut o = ipm_solve_rows<MODE_CADMM, 1, IPM_FAST_REDO, true>(
-          rows_needed(P[i].emask), PlainRef<QPShared>{&S}, EnvPlain{&E[i]}, RtPtr{Rt_all + 9 * i}, P[i], feq + 3 * i, y,
-          w, best, 50, 1e-10, in_tail ? wrec[i] : nullptr, wson);
-      unclean = unclean || o.stiff;
-      ++*qp;
-      *ipm += o.iters;
+  CadmmEnvSlots env[NMAXC];
+  cadmm_env_of_trees(prm, n, st, trees, nt, env);
+  int qstatus[NMAXC];
+  cadmm_host_step(prm, n, st, acc, cadmm_step_cfg(c.nforest > 0), env, c.cf.data() + (size_t)sc * n * N3,
+                  c.cfbar.data() + (size_t)sc * N3, c.clam.data() + (size_t)sc * n * N3, &c.iters[sc],
+                  c.fdes.data() + (size_t)sc * N3, nullptr, qstatus,
+                  [&](int, int, const QPLane<1>& P, const IPMOut& o, bool) {
+                    ++*qp;
+                    *ipm += o.iters;
 #if defined(DAT_IPM_STATS)
-      ++g_ith[P[i].tuned ? 1 : 0][__builtin_popcount(P[i].emask) & 7][o.iters < 31 ? o.iters : 31];
+                    ++g_ith[P.tuned ? 1 : 0][__builtin_popcount(P.emask) & 7][o.iters < 31 ? o.iters : 31];
+#else
+                    (void)P;
 #endif
-      cadmm_take_solve(o, cf + i * N3, y[0], Rt_all, 9, lam + i * N3, fb, rho, n, i, feq);
-    }
-    in_tail = in_tail || (unclean && c.nforest > 0);
-    ++it;
-    rho = std::min(rho * tau, rho_max);
-    for (int j = 0; j < n; ++j) cadmm_mean_block(cf, n, j, fb + 3 * j);
-    double res = 0.0;
-    for (int i = 0; i < n; ++i) res = std::max(res, cadmm_total_res(cf + i * N3, fb, n));
-    if (res < tol || it > max_iter) break;
-    for (int i = 0; i < n; ++i) cadmm_dual_update(lam + i * N3, cf + i * N3, fb, rho, n);
-  }
-  double* fd = c.fdes.data() + (size_t)sc * N3;
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < 3; ++k) fd[3 * i + k] = cf[i * N3 + 3 * i + k];
-  c.iters[sc] = it;
+                  });
 }
 }  // namespace
 

@@ -197,6 +197,7 @@ EXPORTS = {
     "dat_set_persistent_blocks": (ctypes.c_int, [H, ctypes.c_int]),
     "dat_cadmm_slots": (ctypes.c_int, [H, ctypes.c_int, I]),
     "dat_debug_row_modes": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dat_debug_tail_rule": (ctypes.c_int, [H, ctypes.c_int, ctypes.c_int]),
     "dat_cadmm_row_mode": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dat_env_rows": (ctypes.c_int, [H, D, D, I, U8, D]),
     "dat_solve_agent_qp_batch": (ctypes.c_int, [H, ctypes.c_int, I, I, D, D, D, D, D, D, I, I, U8, D]),

@@ -245,6 +245,12 @@ class BatchedController:
         m0, m1, m2 = (-1, -1, -1) if modes is None else (int(m) for m in modes)
         L.check(self._lib.dat_debug_row_modes(self._h, m0, m1, m2))
 
+    def debug_tail_rule(self, tail_prev: Optional[int] = None, tail_pass: Optional[int] = None) -> None:
+        """dat_debug_tail_rule (tests): the tail rule with (tail_prev, tail_pass) instead of the library's pair; None
+        returns to it."""
+        pair = (-1, -1) if tail_prev is None or tail_pass is None else (int(tail_prev), int(tail_pass))
+        L.check(self._lib.dat_debug_tail_rule(self._h, *pair))
+
     def reset_warm_start(self) -> None:
         L.check(self._lib.dat_reset_warm_start(self._h))
 

@@ -10,6 +10,7 @@
 #include <chrono>
 
 #include "dat_handle.hpp"
+#include "dat_cadmm_host.hpp"
 #include "dat_cadmm_lds.hpp"
 
 namespace {
@@ -565,12 +566,13 @@ void dat_default_config(dat_config* c) {
   c->batch = 1;
   c->dt = 1e-3;
   c->hl_every = 10;
-  c->max_iter = 100;
-  c->res_tol = 1e-2;
-  c->use_total_res = 1;
-  c->rho0 = 1.0;
-  c->tau_incr = 1.0;
-  c->rho_max = 2.0;
+  const CadmmStepCfg d;  // the step's defaults, stated once for the handle and the host step
+  c->max_iter = d.max_iter;
+  c->res_tol = d.res_tol;
+  c->use_total_res = d.use_total_res;
+  c->rho0 = d.rho0;
+  c->tau_incr = d.tau;
+  c->rho_max = d.rho_max;
   c->record_err = 0;
 }
 
@@ -1166,6 +1168,20 @@ int dat_debug_row_modes(dat_handle* h, int m0, int m1, int m2) {
   if (!cadmm_rms_built(rm_pack(m0, m1, m2)))
     return fail("dat_debug_row_modes: k_cadmm is not built for these row modes (DAT_CADMM_RMS)");
   h->force_rms = rm_pack(m0, m1, m2);
+  return 0;
+}
+
+int dat_debug_tail_rule(dat_handle* h, int tail_prev, int tail_pass) {
+  if (!h) return fail("dat_debug_tail_rule: null handle");
+  if (h->cfg.mode != DAT_MODE_CADMM) return fail("dat_debug_tail_rule: C-ADMM handles only");
+  if (tail_prev < 0 && tail_pass < 0) {
+    h->tail_prev = TAIL_PREV;
+    h->tail_pass = TAIL_PASS;
+    return 0;
+  }
+  if (tail_prev < 0 || tail_pass < 2) return fail("dat_debug_tail_rule: tail_prev >= 0 and tail_pass >= 2");
+  h->tail_prev = tail_prev;
+  h->tail_pass = tail_pass;
   return 0;
 }
 

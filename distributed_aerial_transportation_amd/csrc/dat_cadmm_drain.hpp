@@ -177,7 +177,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
         kstep = rr[RRES_KSTEP];
         iter = rr[RRES_PASS];
         rmask = rr[RRES_LANES];
-        for (int q = 0; q < iter; ++q) rho = fmin(rho * a.tau, a.rho_max);  // the pass's rho, as k_cadmm had it
+        for (int q = 0; q < iter; ++q) rho = cadmm_next_rho(rho, a.tau, a.rho_max);  // the pass's rho, as k_cadmm had it
         qstat = a.qstatus[(size_t)sc * n + i];  // the pass's status of a lane not solved again
       }
       rebuild = true;
@@ -316,7 +316,7 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     }
     if (active) {
       ++iter;
-      rho = fmin(rho * a.tau, a.rho_max);
+      rho = cadmm_next_rho(rho, a.tau, a.rho_max);
       cadmm_mean_block(cfs, n, i, myred);
     }
     __syncthreads();
@@ -333,21 +333,8 @@ __device__ __forceinline__ void cadmm_drain(const KArgs& a) {
     }
     __syncthreads();
     if (active && i == 0 && vi == 0) {
-      double res = 0.0;
-      const double* rg = L.red + (ls * n) * RDS;
-      if (a.use_total_res) {
-        for (int k = 0; k < n; ++k) res = fmax(res, rg[RDS * k + 6]);
-      } else {
-        for (int r = 0; r < 3; ++r) {
-          double sF = 0.0, sM = 0.0;
-          for (int k = 0; k < n; ++k) {
-            sF += fabs(rg[RDS * k + r]);
-            sM += fabs(rg[RDS * k + 3 + r]);
-          }
-          res = fmax(res, fmax(sF, sM));
-        }
-      }
-      bool stop = (res < a.res_tol) || (iter > a.max_iter);
+      const double res = cadmm_pass_residual(L.red + (ls * n) * RDS, RDS, n, a.use_total_res);
+      const bool stop = cadmm_stop(res, a.res_tol, iter, a.max_iter);
       if (!stop && a.record_err && a.err) a.err[(size_t)sc * (a.max_iter + 1) + iter - 1] = res;
       L.done[ls] = stop ? 1 : 0;
     }

@@ -1,7 +1,8 @@
 // dat_cadmm_step.hpp -- the lane-level rules of the C-ADMM control step (control/rqp_cadmm.py:631-675), each
-// stated once for every build that runs the step: the GPU drain (cadmm_drain, dat_cadmm_drain.hpp; k_agent_qp), the CPU
-// baseline (cpu_baseline/dat_cpu.hip) and the test-only host build (tests/hostsim).  A GPU lane calls them for
-// its agent i between the drain's barriers; a host build calls them in a loop over i < n.  Every floating-point
+// stated once for every build that runs the step: the GPU drain (cadmm_drain, dat_cadmm_drain.hpp; k_agent_qp) and the
+// host step (cadmm_host_step, dat_cadmm_host.hpp: the CPU baseline cpu_baseline/dat_cpu.hip and the test-only host
+// build tests/hostsim run it).  A GPU lane calls them for its agent i between the drain's barriers; the host step
+// calls them in a loop over i < n.  Every floating-point
 // expression stands whole inside one function: with -ffp-contract=on (multiply-adds fused within an expression
 // only) an inlined copy computes the same bits at every call site.
 #pragma once
@@ -20,11 +21,18 @@ DAT_HD bool tail_wedged(int prev_iter, int tail_prev) { return prev_iter > tail_
 DAT_HD bool tail_rule(int pass, int prev_iter, int tail_prev, int tail_pass) {
   return pass >= 1 && (tail_wedged(prev_iter, tail_prev) || pass >= tail_pass);
 }
-// The host models' rule for the passes that keep the agent QPs' warm-start records (kept: the step's earlier
-// passes did; it starts as tail_wedged, and an unclean pass sets it for the passes after it).  The GPU's tail
-// also records inside the pass it resumes, so the two differ when k_cadmm hands over in pass TAIL_PASS - 1: the
-// GPU's handed-over lanes then warm-start pass TAIL_PASS, the host models run it cold.
-DAT_HD bool tail_keeps_records(bool kept, int pass, int tail_pass) { return kept || pass >= tail_pass; }
+// Which agent QPs leave a warm-start record, as k_cadmm and k_cadmm_tail between them apply it: the tail records
+// every solve it runs, k_cadmm none.  The tail owns pass p -- it runs all of the pass's solves -- when the step was
+// wedged from its start, when p >= tail_pass, or when an earlier pass of the step was unclean (k_cadmm handed the
+// scenario over there).
+DAT_HD bool tail_owns_pass(int pass, int prev_iter, int tail_prev, int tail_pass, bool unclean_before) {
+  return tail_wedged(prev_iter, tail_prev) || pass >= tail_pass || unclean_before;
+}
+// Agent i's record of pass p is kept when the tail owns p, or when i's own solve in p was redone (IPMOut::stiff of
+// IPM_FAST_REDO: its fast attempt was unclean, so k_cadmm hands that solve over and the tail runs it again with the
+// record).  The host step (dat_cadmm_host.hpp) solves with a record buffer in every pass and drops the records this
+// rule does not keep; a record is read only under tail_rule, in a pass the tail owns.
+DAT_HD bool tail_keeps_record(bool owns_pass, const IPMOut& o) { return owns_pass || o.stiff != 0; }
 // The IPM's tuned start (ipm_solve): the step's first pass, or the warm closed-loop regime.
 DAT_HD bool cadmm_tuned_start(int pass, int prev_iter) { return pass == 0 || prev_iter <= 3; }
 
@@ -106,6 +114,32 @@ DAT_HD void cadmm_aggregate_res(const double* cfs, const double* f, const double
 DAT_HD void cadmm_dual_update(double* lam, const double* f, const double* fbar, double rho, int n) {
   for (int c = 0; c < 3 * n; ++c) lam[c] += rho * (f[c] - fbar[c]);
 }
+// The pass's residual from the agents' partials (red: n records `stride` doubles apart -- the aggregate's F / M
+// totals at [0, 6), the total residual at [6]; one lane of the slot reduces them): the largest total residual, or
+// for the aggregate the largest row sum of |E_F| and of |E_M| (control/rqp_cadmm.py:582-621).
+DAT_HD double cadmm_pass_residual(const double* red, int stride, int n, bool use_total_res) {
+  double res = 0.0;
+  if (use_total_res) {
+    for (int k = 0; k < n; ++k) res = fmax(res, red[stride * k + 6]);
+  } else {
+    for (int r = 0; r < 3; ++r) {
+      double sF = 0.0, sM = 0.0;
+      for (int k = 0; k < n; ++k) {
+        sF += fabs(red[stride * k + r]);
+        sM += fabs(red[stride * k + 3 + r]);
+      }
+      res = fmax(res, fmax(sF, sM));
+    }
+  }
+  return res;
+}
+// The stop test after `iter` passes (control/rqp_cadmm.py:661) and the next pass's rho (:657-658).  (res_tol and
+// max_iter by reference: the drain reads KArgs::max_iter only where the first test fails, as its inline text did;
+// by value the kernels' code changes.)
+DAT_HD bool cadmm_stop(double res, const double& res_tol, int iter, const int& max_iter) {
+  return (res < res_tol) || (iter > max_iter);
+}
+DAT_HD double cadmm_next_rho(double rho, double tau, double rho_max) { return fmin(rho * tau, rho_max); }
 
 // ------------------------------------------------------------------ the agent QP from caller-supplied rows
 // compacted rows (nenv x 3, nenv: slots 0 .. nenv - 1) -> slot arrays; returns the slot mask

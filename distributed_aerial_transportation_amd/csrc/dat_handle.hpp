@@ -87,6 +87,7 @@ struct dat_handle {
   double cadmm_ms = 0.0;         // summed device time of k_cadmm
   int persistent_blocks = 1024;  // C-ADMM: resident k_cadmm blocks (CUs x 4 wavefronts)
   int force_rms = -1;            // dat_debug_row_modes: k_cadmm's row modes (rm_pack) instead of the rule's; -1: the rule's
+  int tail_prev = TAIL_PREV, tail_pass = TAIL_PASS;  // the tail rule with a forest (dat_debug_tail_rule: another pair)
   double qp_tol = IPM_TOL;       // IPM stopping tolerance (dat_set_qp_tolerance)
   double* params = nullptr;
   int ppp = 0;
@@ -338,8 +339,8 @@ inline KArgs kargs(const dat_handle* h, bool route = false) {
   a.track_pp = h->track_pp;
   a.tick = h->clock;
   a.dt = c.dt;
-  a.tail_prev = h->nforest > 0 ? TAIL_PREV : INT_MAX;
-  a.tail_pass = h->nforest > 0 ? TAIL_PASS : INT_MAX;
+  a.tail_prev = h->nforest > 0 ? h->tail_prev : INT_MAX;
+  a.tail_pass = h->nforest > 0 ? h->tail_pass : INT_MAX;
   a.route = route;
   a.tmode = 0;
 #ifdef DAT_NO_TAIL  // A/B builds only (tools/build_var.sh): the round-5 schedule, no tail rule

@@ -199,6 +199,9 @@ DAT_HD constexpr int best_size(int NB) {
 }
 // Clarabel's own tolerance: an in-band exit whose merit is above it is one Clarabel would not certify
 constexpr double IPM_CLARABEL_TOL = 1e-8;
+// the IPM's iteration cap and default stopping tolerance (dat_set_qp_tolerance), for the kernels and the host step
+constexpr int IPM_MAX_ITER = 50;
+constexpr double IPM_TOL = 1e-10;
 
 // Warm start (start 3, ipm_solve WS): the previous ADMM pass's last iterate of the same agent QP (of a converged,
 // stall-exited or in-band OPTIMAL solve), in a lane record of WREC_SIZE doubles -- [0] valid flag, y (3), w (6),

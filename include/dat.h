@@ -436,6 +436,10 @@ int dat_cadmm_slots(dat_handle* h, int batch, int* slots);
  * the mode triples the rule can give only: any other is refused here, and a control step whose carve by the forced
  * modes would exceed a workgroup's dynamic LDS fails without a launch.  Results do not depend on the modes. */
 int dat_debug_row_modes(dat_handle* h, int m0, int m1, int m2);
+/* Tests: the tail rule of the following control steps with (tail_prev, tail_pass) instead of the library's pair
+ * (tail_prev >= 0, tail_pass >= 2; a negative pair returns to it), so that a small case reaches the hand-over in
+ * the pass before the rule's first.  With a forest only: without one the rule stays out of reach. */
+int dat_debug_tail_rule(dat_handle* h, int tail_prev, int tail_pass);
 int dat_cadmm_row_mode(int n, int slots, int env_class);
 /* Summed device time [ms] since the last counter reset of the main solver kernel of each control step:
  * k_cadmm (C-ADMM) or k_dd (DD; the per-scenario quasi-Newton setup k_dd_setup excluded), 0 for

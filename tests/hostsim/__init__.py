@@ -58,16 +58,17 @@ def qp_cadmm_ex(prm, n, st, acc, lhs, rhs, i, lam, fbar, rho=1.0, tuned=0):
 
 
 def _qp_consts():
-    """WREC_SIZE and the tail rule (TAIL_PREV, TAIL_PASS) as dat_qp.hpp defines them"""
+    """WREC_SIZE and the tail rule (TAIL_PREV, TAIL_PASS) as dat_qp.hpp defines them, DAT_NENV as dat_layout.h"""
     import re
 
     src = open(os.path.join(CORE, "dat_qp.hpp")).read()
     tp = re.search(r"constexpr int TAIL_PREV = (\d+), TAIL_PASS = (\d+);", src)
-    assert tp and "constexpr int WREC_SIZE = 28 + 2 * DAT_MAXROW;" in src
-    return 28 + 2 * 13, int(tp.group(1)), int(tp.group(2))
+    ne = re.search(r"#define DAT_NENV (\d+)", open(os.path.join(CORE, "dat_layout.h")).read())
+    assert tp and ne and "constexpr int WREC_SIZE = 28 + 2 * DAT_MAXROW;" in src
+    return 28 + 2 * 13, int(tp.group(1)), int(tp.group(2)), int(ne.group(1))
 
 
-WREC_SIZE, TAIL_PREV, TAIL_PASS = _qp_consts()
+WREC_SIZE, TAIL_PREV, TAIL_PASS, NENV = _qp_consts()
 
 
 def qp_cadmm_warm(prm, n, st, acc, lhs, rhs, i, lam, fbar, rho, wrec, wson=True, tuned=0):
@@ -82,11 +83,6 @@ def qp_cadmm_warm(prm, n, st, acc, lhs, rhs, i, lam, fbar, rho, wrec, wson=True,
                                     ctypes.c_double(rho), int(tuned), wrec.ctypes.data_as(D), int(bool(wson)), f.ctypes.data_as(D),
                                     ctypes.byref(it), ctypes.byref(ib))
     return f, status, it.value, ib.value
-
-
-def tail_rule(ps, prev):
-    """the tail rule names pass ps of a step whose previous step took prev passes (tail_rule, dat_cadmm_step.hpp)"""
-    return bool(lib().hs_tail_rule(int(ps), int(prev)))
 
 
 def last_stiff():
@@ -161,6 +157,69 @@ def dd_step(prm, n, st, acc, warm, trees=None, res_tol=1e-2, max_iter=100, qp_to
     return DDStep(f.T.copy(), it, err[: it - 1].copy(), qs, ipmx.value)
 
 
+class CadmmStep:
+    """one C-ADMM control step of the host build: f_des (3, n), iters, err_seq (iters - 1), qp_status (n) and the
+    observer's counts of the step's agent-QP solves -- solves, ipm_iters, redone (fast attempt unclean), warm
+    (started from the record), loose (accepted in band beyond Clarabel's 1e-8); per pass (iters each) pass_ipmx, the
+    slowest solve's IPM iterations, and pass_warm / pass_redone, the agents (bit i) started warm / redone"""
+
+    def __init__(self, f_des, iters, err_seq, qp_status, counts, pass_ipmx, pass_warm, pass_redone):
+        self.f_des, self.iters, self.err_seq, self.qp_status = f_des, iters, err_seq, qp_status
+        self.solves, self.ipm_iters, self.redone, self.warm, self.loose = (int(c) for c in counts)
+        self.pass_ipmx, self.pass_warm, self.pass_redone = pass_ipmx, pass_warm, pass_redone
+
+
+def cadmm_warm(prm, n):
+    """a C-ADMM controller's warm state before its first step (control/rqp_cadmm.py:577-580): cf (n, 3n) and fbar
+    (3n) at f_eq, lam (n, 3n) zero, and the previous step's pass count (1 int32: none yet)"""
+    from distributed_aerial_transportation_amd import layout
+
+    feq = np.asarray(prm, dtype=np.float64)[layout.p_off("FEQ", n):][: 3 * n]
+    return np.tile(feq, (n, 1)), feq.copy(), np.zeros((n, 3 * n)), np.zeros(1, dtype=np.int32)
+
+
+def cadmm_step(prm, n, st, acc, warm, trees=None, rows=None, tail=(TAIL_PREV, TAIL_PASS), res_tol=1e-2, max_iter=100,
+               qp_tol=1e-10, use_total_res=True, rho0=1.0, tau=1.0, rho_max=2.0):
+    """hs_cadmm_step: one whole C-ADMM control step of one scenario in the drain's sequence (cadmm_host_step,
+    csrc/dat_cadmm_host.hpp).  warm = (cf, fbar, lam, prev_iters) of cadmm_warm, updated in place (the controller's
+    state from step to step).  The env rows: from trees (T, 3), sorted by x here as dat_set_forests sorts each forest,
+    or from rows, per agent the compacted (lhs (k, 3), rhs (k)).  tail = (tail_prev, tail_pass) of the tail rule;
+    without trees and rows the rule is out of reach, as on the GPU without a forest."""
+    cf, fbar, lam, prev = warm
+    for a, size in ((cf, 3 * n * n), (fbar, 3 * n), (lam, 3 * n * n)):
+        assert a.dtype == np.float64 and a.flags.c_contiguous and a.size == size
+    assert prev.dtype == np.int32 and prev.size == 1
+    nt = 0 if trees is None else len(trees)
+    if nt:
+        trees = np.asarray(trees, dtype=np.float64)
+        trees = np.ascontiguousarray(trees[np.argsort(trees[:, 0], kind="stable")])
+    lhs = rhs = nrow = None
+    if rows is not None:
+        lhs, rhs, nrow = np.zeros((n, NENV, 3)), np.zeros((n, NENV)), np.zeros(n, dtype=np.int32)
+        for i, (L, R) in enumerate(rows):
+            L = np.asarray(L, dtype=np.float64).reshape(-1, 3)
+            nrow[i] = L.shape[0]
+            lhs[i, : nrow[i]], rhs[i, : nrow[i]] = L, R
+    if trees is None and rows is None:
+        tail = (2**31 - 1, 2**31 - 1)
+    cfgd = np.array([res_tol, rho0, tau, rho_max, qp_tol], dtype=np.float64)
+    cfgi = np.array([max_iter, int(bool(use_total_res)), tail[0], tail[1]], dtype=np.int32)
+    f = np.zeros((n, 3))
+    err = np.zeros(max_iter + 1)
+    qs = np.zeros(n, dtype=np.int32)
+    counts = np.zeros(5, dtype=np.int64)
+    per_pass = np.zeros((3, max_iter + 1), dtype=np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(I)  # noqa: E731
+    rc = lib().hs_cadmm_step(p(prm), n, p(st), p(acc), p(trees) if nt else None, nt, None if lhs is None else p(lhs),
+                             None if rhs is None else p(rhs), ip(nrow), p(cfgd), ip(cfgi), cf.ctypes.data_as(D),
+                             fbar.ctypes.data_as(D), lam.ctypes.data_as(D), ip(prev), f.ctypes.data_as(D),
+                             err.ctypes.data_as(D), ip(qs), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                             ip(per_pass[0]), ip(per_pass[1]), ip(per_pass[2]))
+    assert rc == 0, rc
+    it = int(prev[0])
+    return CadmmStep(f.T.copy(), it, err[: it - 1].copy(), qs, counts, *(per_pass[k, :it].copy() for k in range(3)))
+
+
 def qp_cent(prm, n, st, acc, lhs, rhs):
     f = np.zeros(3 * n)
     it = ctypes.c_int()
@@ -181,6 +240,13 @@ def env_rows(prm, n, st, trees, agent, alpha):
     k = lib().hs_env_rows(p(prm), n, p(st), p(trees), trees.shape[0], agent, ctypes.c_double(alpha),
                           lhs.ctypes.data_as(D), rhs.ctypes.data_as(D), ctypes.byref(col), ctypes.byref(md))
     return lhs[:k], rhs[:k], bool(col.value), md.value
+
+
+def desired_accel(st, n, mountain, x_offset=1.5):
+    """the forest scenario's desired payload acceleration (desired_accel_forest; mountain: system.pack_mountain)"""
+    acc = np.zeros(6)
+    lib().hs_desired_accel(p(st), n, p(mountain), ctypes.c_double(x_offset), acc.ctypes.data_as(D))
+    return acc
 
 
 def sim_step(prm, n, st, counter, fdes, dt, kind=0):

@@ -6,7 +6,7 @@
 // dev container, which has no GPU.  The product path has no CPU fallback.
 #include <vector>
 
-#include "../../distributed_aerial_transportation_amd/csrc/dat_cadmm_step.hpp"
+#include "../../distributed_aerial_transportation_amd/csrc/dat_cadmm_host.hpp"
 #include "../../distributed_aerial_transportation_amd/csrc/dat_dd_step.hpp"
 
 using namespace dat;
@@ -119,8 +119,6 @@ void hs_last_diag(double* merit, int* inband, int* why) {
 
 long long hs_stiff_redos() { return g_stiff_redo; }
 int hs_last_stiff() { return g_last_stiff; }
-// the tail rule names pass `pass` of a step whose previous step took prev_iter passes (with a forest)
-int hs_tail_rule(int pass, int prev_iter) { return tail_rule(pass, prev_iter, TAIL_PREV, TAIL_PASS); }
 
 // as hs_qp_cadmm with k_cadmm's IPM start policy flag (P.tuned) and the in-band exit flag out
 int hs_qp_cadmm_ex(const double* prm, int n, const double* st, const double* acc, const double* env_lhs,
@@ -283,6 +281,49 @@ int hs_dd_step(const double* prm, int n, const double* st, const double* acc, co
   for (int i = 0; i < n; ++i)
     for (int c = 0; c < 3; ++c) f_des[3 * i + c] = X[9 * i + c];
   return iter;
+}
+
+// One C-ADMM control step of one scenario: cadmm_host_step (dat_cadmm_host.hpp).  The env rows come from the
+// scenario's forest sorted by x (trees, ntree x 3; no rows pointer), or from the caller's compacted rows (row_lhs
+// n x DAT_NENV x 3, row_rhs n x DAT_NENV, nrow n).  cfgd: res_tol, rho0, tau, rho_max, qp_tol; cfgi: max_iter,
+// use_total_res, tail_prev, tail_pass.  In / out: the warm state cf, fbar, lam and *iters (the previous step's pass
+// count in, this step's out).  Out: f_des, err_seq (max_iter + 1), qstatus (n) and what the observer counted --
+// counts: solves, IPM iterations, redone solves, warm-started solves, loose accepts beyond Clarabel's 1e-8; per pass
+// (max_iter + 1 each) the slowest solve's IPM iterations and the agents (bit i) warm-started and redone.
+int hs_cadmm_step(const double* prm, int n, const double* st, const double* acc, const double* trees, int ntree,
+                  const double* row_lhs, const double* row_rhs, const int* nrow, const double* cfgd, const int* cfgi,
+                  double* cf, double* fbar, double* lam, int* iters, double* f_des, double* err_seq, int* qstatus,
+                  long long* counts, int* pass_ipmx, int* pass_warm, int* pass_redone) {
+  if (n < 3 || n > CADMM_HOST_NMAX) return -1;
+  CadmmStepCfg cfg;
+  cfg.res_tol = cfgd[0]; cfg.rho0 = cfgd[1]; cfg.tau = cfgd[2]; cfg.rho_max = cfgd[3]; cfg.qp_tol = cfgd[4];
+  cfg.max_iter = cfgi[0]; cfg.use_total_res = cfgi[1]; cfg.tail_prev = cfgi[2]; cfg.tail_pass = cfgi[3];
+  CadmmEnvSlots env[CADMM_HOST_NMAX];
+  if (row_lhs) {
+    for (int i = 0; i < n; ++i) {
+      if (nrow[i] < 0 || nrow[i] > DAT_NENV) return -1;
+      cadmm_env_of_rows(row_lhs + (size_t)i * DAT_NENV * 3, row_rhs + (size_t)i * DAT_NENV, nrow[i], env[i]);
+    }
+  } else {
+    cadmm_env_of_trees(prm, n, st, trees, ntree, env);
+  }
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  for (int k = 0; k <= cfg.max_iter; ++k) pass_ipmx[k] = pass_warm[k] = pass_redone[k] = 0;
+  cadmm_host_step(prm, n, st, acc, cfg, env, cf, fbar, lam, iters, f_des, err_seq, qstatus,
+                  [&](int pass, int i, const QPLane<1>&, const IPMOut& o, bool warm) {
+                    ++counts[0];
+                    counts[1] += o.iters;
+                    // (a warm solve's first attempt is the robust one, whose IPMOut::stiff means stiff rows)
+                    const bool redone = o.stiff && !warm;
+                    counts[2] += redone;
+                    counts[3] += warm;
+                    counts[4] += o.inband && o.merit > IPM_CLARABEL_TOL;
+                    if (o.iters > pass_ipmx[pass]) pass_ipmx[pass] = o.iters;
+                    pass_warm[pass] |= (warm ? 1 : 0) << i;
+                    pass_redone[pass] |= (redone ? 1 : 0) << i;
+                    diag(o);
+                  });
+  return 0;
 }
 
 int hs_qp_cent(const double* prm, int n, const double* st, const double* acc, const double* env_lhs,

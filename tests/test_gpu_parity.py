@@ -448,3 +448,51 @@ def test_gpu_dd_step_matches_host_step(n, B, forest):
             assert _rel(r.f_des[b], h.f_des) < REL, (b, _rel(r.f_des[b], h.f_des))
             np.testing.assert_allclose(r.err_seq[b, : h.iters - 1], h.err_seq, rtol=ERR_RTOL, atol=ERR_ATOL)
             assert np.array_equal(r.qp_status[b], h.qp_status), (b, r.qp_status[b], h.qp_status)
+
+
+@pytest.mark.parametrize("n,B,forest", [(3, 22, False), (16, 5, False), (6, 11, True)])
+def test_gpu_cadmm_step_matches_host_step(n, B, forest):
+    """k_cadmm / k_cadmm_tail against the host statement of the same step (csrc/dat_cadmm_host.hpp, tests/hostsim
+    hs_cadmm_step), two steps each (warm copies, mean and multipliers carried): iteration counts exact, f_des within
+    1e-5, residual sequences within ERR_RTOL / ERR_ATOL (the host build fuses its multiply-adds differently, so the
+    match is not bitwise).  One scenario more than the G = floor(64 / n) slots of a workgroup, so every shape refills
+    a slot: n = 3 (G = 21), n = 16 (G = 4), and n = 6 (G = 10) in the crowd forest of tests/_envscenes.py, whose trees
+    put env rows on some agents (env classes above 0, the tail rule in reach).  A scenario whose host residual
+    sequence comes within the band of the tolerance (_ambiguous) is left out, at most one per shape."""
+    from distributed_aerial_transportation_amd import scenarios
+    from tests import hostsim as hs
+
+    prm = scenarios.params_block(n)
+    rng = np.random.default_rng(1900 + 10 * n + forest)
+    eng = _eng("cadmm", n, B, record_err=True)
+    eng.set_persistent_blocks(1)
+    trees = None
+    if forest:
+        from tests import _envscenes as es
+        from tests.test_gpu_env_rows_reference import _forest
+
+        cases = es.battery(n)[0]
+        trees = next(c for c in cases if c.name == "crowd").trees
+        states = np.stack([c.state for c in cases[:B]])
+        eng.set_forests([_forest(trees)])
+        rows = sum(len(hs.env_rows(prm, n, x, trees, i, es.ALPHA_D)[1]) for x in states for i in range(n))
+        assert rows > 0
+        acc = np.concatenate([rng.uniform(-1, 1, (B, 3)), np.zeros((B, 3))], axis=1)
+    else:
+        states = scenarios.perturbed_states(n, B, rng)
+        acc = np.concatenate([rng.uniform(-3, 3, (B, 3)), rng.uniform(-3, 3, (B, 3))], axis=1)
+    r1 = eng.control(states, acc)
+    r2 = eng.control(states, acc[::-1].copy())
+    skipped = 0
+    for b in range(B):
+        warm = hs.cadmm_warm(prm, n)
+        hosts = [hs.cadmm_step(prm, n, states[b], a, warm, trees) for a in (acc[b], acc[B - 1 - b])]
+        if any(_ambiguous(h.err_seq) for h in hosts):
+            skipped += 1
+            continue
+        for r, h in zip((r1, r2), hosts):
+            assert r.iters[b] == h.iters, (b, r.iters[b], h.iters)
+            assert _rel(r.f_des[b], h.f_des) < REL, (b, _rel(r.f_des[b], h.f_des))
+            np.testing.assert_allclose(r.err_seq[b, : h.iters - 1], h.err_seq, rtol=ERR_RTOL, atol=ERR_ATOL)
+            assert np.array_equal(r.qp_status[b], h.qp_status), (b, r.qp_status[b], h.qp_status)
+    assert skipped <= 1, skipped

@@ -1,6 +1,7 @@
-"""CPU proxy of tests/test_gpu_hard_stretch.py: the oracle's C-ADMM / DD outer loop with every agent QP
-answered by the device code's host build (tests/hostsim) instead of the oracle IPM, compared with the
-fixture (f_des per HL step, outer iteration counts).
+"""CPU proxy of tests/test_gpu_hard_stretch.py: the C-ADMM control step of the device code's host build
+(hs.cadmm_step, on the oracle's env rows), or the oracle's DD outer loop with every agent QP answered by the host
+build instead of the oracle IPM, compared with the fixture (f_des per HL step, outer iteration counts; C-ADMM: the
+agents whose last QP was not OPTIMAL).
 
     python tools/hard_loop_hostsim.py cadmm|dd [hostsim .so]
 """
@@ -31,21 +32,10 @@ def main():
     prm = scenarios.params_block(n)
     np.random.seed(0)
     forest = of.Forest()
-    ctl = (oc.CADMM if kind == "cadmm" else oc.DD)(p, osc.col_radius(n), forest)
+    ctl = oc.DD(p, osc.col_radius(n), forest)  # (the dd kind's outer loop; cadmm runs hs.cadmm_step)
     s = RQPState.unpack(d["x0"], n)
     st = om.State(s.R, s.w, s.xl, s.vl, s.Rl, s.wl, project=False)
     bad = [0]
-
-    def cadmm_solve(self, i, s_, acc, env, rho):
-        lam = self.lam[:, :, i].T.reshape(-1).copy()
-        fbar = self.f_mean.T.reshape(-1).copy()
-        f, status, it, ib = hs.qp_cadmm_ex(prm, n, pack_state(s_), np.concatenate(acc), env.lhs, env.rhs, i, lam, fbar,
-                                           rho)
-        if status == 0:
-            self.prev_f[i] = f.reshape(n, 3).T.copy()
-        else:
-            bad[0] += 1
-        return self.prev_f[i], None
 
     def dd_solve(self, i, s_, acc, env, cf, cF, cM):
         x, status, it = hs.qp_dd(prm, n, pack_state(s_), np.concatenate(acc), env.lhs, env.rhs, i,
@@ -56,17 +46,24 @@ def main():
             bad[0] += 1
         return self.prev[i], None
 
-    oc.CADMM.solve_agent = cadmm_solve
     oc.DD.solve_agent = dd_solve
+    c = om.Consts.make(p, osc.col_radius(n), distributed=True)
+    warm = hs.cadmm_warm(prm, n)
     worst = 0.0
     for k in range(d["f_des"].shape[0]):
         bad[0] = 0
         acc, _, _ = oc.desired_acceleration_forest(st, forest)
-        f, stat = ctl.control(st, acc)
+        if kind == "cadmm":  # the whole step by the host build (hs.cadmm_step) on the oracle's env rows
+            envs = [of.env_rows(forest, c, st, osc.col_radius(n), p.r[:, i]) for i in range(n)]
+            r = hs.cadmm_step(prm, n, pack_state(st), np.concatenate(acc), warm, rows=[(e.lhs, e.rhs) for e in envs])
+            f, iters, bad[0] = r.f_des, r.iters, int(np.sum(r.qp_status != 0))
+        else:
+            f, stat = ctl.control(st, acc)
+            iters = stat.iter
         ref = d["f_des"][k]
         rel = np.max(np.abs(f - ref)) / max(1.0, np.max(np.abs(ref)))
         worst = max(worst, rel)
-        print(f"step {k:2d}: iters {stat.iter:3d} (ref {int(d['iters'][k]):3d})  f_des rel diff {rel:.2e}  "
+        print(f"step {k:2d}: iters {iters:3d} (ref {int(d['iters'][k]):3d})  f_des rel diff {rel:.2e}  "
               f"non-optimal QPs {bad[0]}", flush=True)
         for _ in range(10):
             fl, M = om.low_level_control(p, st, f)

@@ -1,7 +1,7 @@
 """Does the host build of the QP solvers give the same bits in two builds?  Runs the agent-QP checks of
 tests/test_hostsim.py -- the C-ADMM, DD and centralized QPs against the oracle, the C4 stall stretches of
-ref_c4_hard.npz (cold, tuned and warm solves through the tail rule), the captured loose QPs of ref_loose_caps.npz and
-the host DD steps -- once with each of two builds of tests/hostsim/hostsim.hip,
+ref_c4_hard.npz (whole C-ADMM steps: cold, tuned and warm solves through the tail rule), the captured loose QPs of
+ref_loose_caps.npz and the host DD steps -- once with each of two builds of tests/hostsim/hostsim.hip,
 
     hipcc -O2 -std=c++17 -fPIC -shared --offload-arch=gfx950 tests/hostsim/hostsim.hip -o X.so
 
@@ -21,10 +21,11 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY = ("qp_cadmm", "qp_cadmm_ex", "qp_cadmm_warm", "qp_dd", "qp_cent", "dd_step")
+ENTRY = ("qp_cadmm", "qp_cadmm_ex", "qp_cadmm_warm", "qp_dd", "qp_cent", "dd_step", "cadmm_step")
 TESTS = ("test_reduced_cadmm_qp_matches_oracle", "test_reduced_dd_qp_matches_oracle",
          "test_reduced_centralized_qp_matches_oracle", "test_c4_stall_stretch_matches_oracle",
-         "test_loose_caps_solved_within_clarabel_tol", "test_host_dd_step_golden", "test_host_dd_step_matches_oracle",
+         "test_c4_tail_record_rule_at_the_handover_pass", "test_loose_caps_solved_within_clarabel_tol",
+         "test_host_dd_step_golden", "test_host_dd_step_matches_oracle",
          "test_host_dd_long_chains_match_oracle")
 
 
@@ -69,6 +70,8 @@ def record(lib, out):
                 fn(*c)
             except AssertionError as ex:  # the comparison is of the solves, whatever the test makes of them
                 print(f"  ({t}{c}: assertion {ex})")
+            except AttributeError as ex:  # a build from before an entry point existed: its entry stays empty
+                print(f"  ({t}{c}: {ex})")
             except pytest.skip.Exception:
                 pass
     with open(out, "wb") as f:

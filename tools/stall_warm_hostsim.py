@@ -1,9 +1,9 @@
-"""The C4 stall stretches (tests/golden/ref_c4_hard.npz) on the host build of the device solver with the tail
-kernel's warm start (an agent QP of ADMM pass >= P0 starts from its converged iterate of the previous pass):
-per HL step the ADMM passes, the critical-path IPM iterations (sum over passes of the slowest agent QP) and
-f_des against the oracle's (the bound of tests/test_gpu_c4_hard.py).  TEST infrastructure (development).
+"""The C4 stall stretches (tests/golden/ref_c4_hard.npz) on the host build of the C-ADMM step (hs.cadmm_step, the
+tail rule's warm start from pass TAIL_PASS, or from the second pass of a step after more than TAIL_PREV passes): per
+HL step the ADMM passes, the critical-path IPM iterations (sum over passes of the slowest agent QP) and f_des against
+the oracle's (the bound of tests/test_gpu_c4_hard.py).  TEST infrastructure (development).
 
-    python tools/stall_warm_hostsim.py [lib.so] [steps] [P0]    (P0 < 0: no warm start)
+    python tools/stall_warm_hostsim.py [lib.so] [steps] [TAIL_PREV TAIL_PASS]    (default: the library's pair)
 """
 import os
 import sys
@@ -19,7 +19,7 @@ if len(sys.argv) > 1 and sys.argv[1] != "-":
     hs.LIB = sys.argv[1]
     hs.build = lambda force=False: hs.LIB  # noqa: E731
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-P0 = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+TAIL = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (hs.TAIL_PREV, hs.TAIL_PASS)
 
 from distributed_aerial_transportation_amd import scenarios  # noqa: E402
 from distributed_aerial_transportation_amd.system import RQPState, pack_state  # noqa: E402
@@ -31,6 +31,7 @@ from oracle import scenarios as osc  # noqa: E402
 d = load("ref_c4_hard.npz")
 n = 6
 p = osc.params(n)
+c = om.Consts.make(p, osc.col_radius(n), distributed=True)
 prm = scenarios.params_block(n)
 tot_crit, tot_fail, worst = 0, 0, 0.0
 for j in range(d["x0"].shape[0]):
@@ -38,61 +39,32 @@ for j in range(d["x0"].shape[0]):
     forest = of.Forest()
     s0 = RQPState.unpack(d["x0"][j], n)
     st = om.State(s0.R, s0.w, s0.xl, s0.vl, s0.Rl, s0.wl, project=False)
-    ctl = oc.CADMM(p, osc.col_radius(n), forest)
-    tally = {"pass": 0, "tuned": 1, "loose": 0, "it": []}
-    wrec = np.zeros((n, hs.WREC_SIZE))
-
-    def solve(self, i, s_, acc, env, rho):
-        lam = self.lam[:, :, i].T.reshape(-1).copy()
-        fbar = self.f_mean.T.reshape(-1).copy()
-        tuned = tally["tuned"] if tally["pass"] == 0 else 0
-        if P0 < 0 or tally["pass"] < P0:
-            wrec[i, 0] = 0.0
-            f, status, its, inb = hs.qp_cadmm_ex(prm, n, pack_state(s_), np.concatenate(acc), env.lhs, env.rhs, i,
-                                                 lam, fbar, rho, tuned=tuned)
-        else:
-            rec = np.ascontiguousarray(wrec[i])
-            f, status, its, inb = hs.qp_cadmm_warm(prm, n, pack_state(s_), np.concatenate(acc), env.lhs, env.rhs, i,
-                                                   lam, fbar, rho, rec, tuned=tuned)
-            wrec[i] = rec
-        tally["loose"] += bool(inb) and hs.last_diag()[0] > 1e-8
-        tally["it"].append(its)
-        if os.environ.get("DUMP") == f"{j},{tally['k']}" and 40 <= tally["pass"] <= 42:
-            print("   pass", tally["pass"], "agent", i, "status", status, "its", its, "inband", inb, "diag", hs.last_diag(), "nenv", len(env.rhs))
-        if status == 0:
-            self.prev_f[i] = f.reshape(n, 3).T.copy()
-        if i == n - 1:
-            tally["pass"] += 1
-            tally["crit"] = tally.get("crit", 0) + max(tally["it"])
-            tally["all"] = tally.get("all", 0) + sum(tally["it"])
-            tally["it"] = []
-        return self.prev_f[i], None
-
-    ctl.solve_agent = solve.__get__(ctl)
-    prev = 0
+    warm = hs.cadmm_warm(prm, n)
+    loose = 0
     for k in range(K):
-        tally["pass"], tally["tuned"], tally["crit"], tally["all"], tally["k"] = 0, 1 if prev <= 3 else 0, 0, 0, k
-        wrec[:] = 0.0
         acc, _, _ = oc.desired_acceleration_forest(st, forest)
-        f, stat = ctl.control(st, acc)
-        prev = stat.iter
+        envs = [of.env_rows(forest, c, st, osc.col_radius(n), p.r[:, i]) for i in range(n)]
+        r = hs.cadmm_step(prm, n, pack_state(st), np.concatenate(acc), warm, rows=[(e.lhs, e.rhs) for e in envs],
+                          tail=TAIL)
+        loose += r.loose
+        crit = int(r.pass_ipmx.sum())
         ref = d["f_des"][j, k]
         scale = max(1.0, np.max(np.abs(ref)))
-        rel = np.max(np.abs(f - ref)) / scale
+        rel = np.max(np.abs(r.f_des - ref)) / scale
         sens = np.max(np.abs(d["f_des_1e10"][j, k] - ref)) / scale
         sens8 = np.max(np.abs(d["f_des_1e8"][j, k] - ref)) / scale
         bound = max(1e-5, 5.0 * sens, sens8)
-        ok = stat.iter == d["iters"][j, k] and rel < bound
+        ok = r.iters == d["iters"][j, k] and rel < bound
         tot_fail += not ok
         if sens < 1e-5:
             worst = max(worst, rel)
-        tot_crit += tally["crit"]
-        print(f"scen {j} step {k:2d}: passes {stat.iter:3d} (ref {d['iters'][j, k]:3d}) f_des rel {rel:.2e} bound "
-              f"{bound:.1e} {'ok' if ok else 'FAIL'}; critical-path IPM it {tally['crit']:5d} "
-              f"({tally['crit'] / max(stat.iter, 1):.1f}/pass), all {tally['all']}", flush=True)
+        tot_crit += crit
+        print(f"scen {j} step {k:2d}: passes {r.iters:3d} (ref {d['iters'][j, k]:3d}) f_des rel {rel:.2e} bound "
+              f"{bound:.1e} {'ok' if ok else 'FAIL'}; critical-path IPM it {crit:5d} "
+              f"({crit / max(r.iters, 1):.1f}/pass), all {r.ipm_iters}, warm {r.warm}, redone {r.redone}", flush=True)
         for _ in range(10):
-            fl, M = om.low_level_control(p, st, f)
+            fl, M = om.low_level_control(p, st, r.f_des)
             st.integrate(*om.forward_dynamics(p, st, fl, M), 1e-3)
-    print(f"scen {j}: loose accepts {tally['loose']}")
+    print(f"scen {j}: loose accepts {loose}")
 print(f"TOTAL critical-path IPM iterations {tot_crit}, failing steps {tot_fail}, worst rel where reproducible "
       f"{worst:.2e}")
